@@ -3,12 +3,14 @@
 clip_grad_norm_ + AdamW) of hierarchical_ordered (G=8, S=30, d_model=256) at 512 icons per GPU, synthetic data,
 on N MI355X (one process per GPU, RCCL gradient all-reduce).
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (contract in the task statement).  The timed loop rotates 8 distinct device-resident batches
-(different layout buckets included; `graphs` reports how many hipGraphs that took).  Extra objects:
+Rank 0 prints ONE JSON line: `value` icons/s and `ms_per_step` of the K timed steps.  The timed loop rotates 8 distinct
+device-resident batches (different layout buckets included; `graphs` reports how many hipGraphs that took).  A plain run sets
+up, warms up, times the K steps and prints the line; `--dump-outputs DIR` also writes what the last timed step computed
+(dump_outputs).  The extra objects below are measured with `--full` only (null in a plain run):
   roofline     the FFN sub-block of the 16 layers (fused forward kernel on the large stages, its share of the fused per-layer
                kernels on the 4096-row stages, the backward launches: dropout replay, gated dX GEMM, fused dx + LayerNorm-
                backward kernel, the weight-gradient GEMMs, the finishing kernel, and its share of the batched gradient
@@ -76,7 +78,19 @@ def parse():
     ap.add_argument("--no-fp32", action="store_true", help="skip the fp32 parity-path sub-record")
     ap.add_argument("--no-extra-legs", action="store_true", help="skip the dense_layout / secondary / in-kernel clock legs")
     ap.add_argument("--cpu-leg", type=int, default=0, help="internal: run one CPU-baseline leg on this many threads and exit")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (sysfs clock sampling, roofline, fp32, dense layout, secondary "
+                         "workloads, in-kernel clock, one-rank RCCL, stock-PyTorch reference, CPU baseline; the --no-* options "
+                         "above switch single legs off again).  Without it the run times the train step and prints its line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float32, < 64 MB): the loss "
+                         "dict, the flat gradient, a fixed sample of the updated parameters")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.ffn_replay > 0 and not a.full:
+        ap.error("--ffn-replay runs after the roofline leg: it needs --full")
+    return a
 
 
 def _oracle_step_fn(cfg, sd, batch, device, dropout, seed=4242):
@@ -541,6 +555,28 @@ def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_PARAM_SAMPLE = 1 << 21     # parameters in the --dump-outputs sample: the whole fp32 image is 41 MB, the gradient beside it
+
+
+def dump_outputs(out_dir, ld, model):
+    """--dump-outputs DIR: what the timed path computed in its LAST step, as float32 .npy files (~50 MB in all) - the loss dict
+    TrainStep.step returned (<key>.npy), the flat gradient of that step (grad.npy, padding slots included) and the parameters
+    after its AdamW update at a fixed, seeded sample of positions of the flat fp32 buffer (params_sample.npy)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    out = {k: v.detach().float().reshape(-1).cpu().numpy() for k, v in ld.items()}
+    store = model.store
+    if store.flat is not None:
+        out["grad"] = store.grad_buffer(0).detach().float().cpu().numpy()
+        flat = store.flat.detach().float().cpu().numpy()
+        n = min(DUMP_PARAM_SAMPLE, flat.size)
+        idx = np.sort(np.random.default_rng(20240611).choice(flat.size, size=n, replace=False))
+        out["params_sample"] = flat[idx]
+    for name, arr in out.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(arr, dtype=np.float32))
+    log(f"outputs of the last timed step -> {out_dir}: " + ", ".join(f"{k} {v.size}" for k, v in out.items()))
+
+
 def main():
     a = parse()
     if a.cpu_leg > 0:
@@ -665,7 +701,7 @@ def main():
     sync()
     captured_before = ts.graphs_captured
     keys_seen, switches, last_key = set(), 0, None
-    sclk = SclkSampler(local_rank) if (rank == 0 and not emulate) else None
+    sclk = SclkSampler(local_rank) if (rank == 0 and a.full and not emulate) else None
     if sclk is not None:
         sclk.__enter__()
     t0 = time.perf_counter()
@@ -690,6 +726,8 @@ def main():
     loss_val = float(ld["loss"])
     assert loss_val == loss_val and abs(loss_val) < 1e4, f"loss diverged: {loss_val}"
     log(f"timed {a.steps} steps in {elapsed:.3f}s, loss {loss_val:.4f}")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, ld, model)       # before any leg below runs another step on the same model
     if ts.host_trace:       # DSVG_TRACE_STEP=1: where the host spends a step (ms): plan + its one read, copies + graph launch
         tr = ts.host_trace[-a.steps:]
         plan_ms = sum(t[1] - t[0] for t in tr) / len(tr) * 1e3
@@ -718,7 +756,7 @@ def main():
                "ms_per_step": round(ms_per_step, 3)}
 
     roofline = None
-    if rank == 0 and not a.no_roofline and not emulate:
+    if rank == 0 and a.full and not a.no_roofline and not emulate:
         # Per-launch times of the FFN sub-block, live: HIP events (torch.cuda.Event on the launch stream) around every tagged
         # launch of the SAME launch sequence the timed step replays - same kernels, same order, deferred + batched gradient
         # reductions - issued eagerly behind a short queue of other GPU work, so that the host has enqueued the step before
@@ -959,9 +997,10 @@ def main():
                 specs = [r[5] for r in ffn[:n_ffn] if "a" in r[5]]
                 replay_ffn(specs, a.ffn_replay, device)
 
-    log(f"roofline leg done: {roofline}")
+    if a.full:
+        log(f"roofline leg done: {roofline}")
     fp32 = None
-    if rank == 0 and world == 1 and a.dtype == "bf16" and not a.no_fp32 and not emulate:
+    if rank == 0 and world == 1 and a.full and a.dtype == "bf16" and not a.no_fp32 and not emulate:
         # the parity path (what the 1e-3 tolerance of the north star is tested on): the same step over the same rotating batches,
         # timed by the same loop as the headline (round 6: hipGraph replay like the bf16 step; eager if a capture fails)
         m32 = deepsvg_amd.SVGTransformer(cfg)
@@ -1020,7 +1059,7 @@ def main():
         del m32, t32
         log(f"fp32 leg done: {fp32}")
     dense = secondary = clock = None
-    if rank == 0 and world == 1 and a.dtype == "bf16" and not a.no_extra_legs and not emulate:
+    if rank == 0 and world == 1 and a.full and a.dtype == "bf16" and not a.no_extra_legs and not emulate:
         try:
             dense = dense_layout_leg(cfg, sd_cpu, batches, device)
         except Exception as e:      # reported, never fatal for the bench line
@@ -1049,7 +1088,7 @@ def main():
             ff["measured_clock_mhz"] = mhz
             ff["chunk_loop_frac_at_its_clock"] = round(
                 2 * 32 * 32.0 / max(clock["cycles_per_chunk"], 1.0), 4)     # matrix-pipe cycles of a SIMD's two waves (2 x 32 MFMAs x 32) / cycles per chunk
-    if ddp is None and rank == 0 and world == 1 and not a.no_extra_legs and not emulate and not (dist.is_available() and dist.is_initialized()):
+    if ddp is None and rank == 0 and world == 1 and a.full and not a.no_extra_legs and not emulate and not (dist.is_available() and dist.is_initialized()):
         # the data-parallel path on a ONE-rank RCCL group (no multi-GPU lease is available to the builder): the same step with the
         # 3-count loss all-reduce in front of the graph and the 41 MB gradient all-reduce behind it - what a rank of an N-GPU
         # run executes, minus the wire.  `allreduce_ms` = the exposed time of that exchange on one GPU (RCCL's local copy path);
@@ -1060,7 +1099,7 @@ def main():
             ddp = {"error": f"{type(e).__name__}: {e}"[:300]}
         log(f"one-rank RCCL leg done: {ddp}")
     torch_ref = None
-    if rank == 0 and world == 1 and not a.no_torch_ref and not emulate:
+    if rank == 0 and world == 1 and a.full and not a.no_torch_ref and not emulate:
         try:
             torch_ref = torch_rocm_reference(cfg, sd_cpu, a.batch, device, a.dropout)
         except Exception as e:          # (e.g. out of memory on a shared box): reported, never fatal for the bench line
@@ -1068,7 +1107,7 @@ def main():
         torch.cuda.empty_cache()
         log(f"torch-ROCm reference leg done: {torch_ref}")
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not emulate:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline and not emulate:
         cpu = cpu_baseline(cfg, sd_cpu, a.cpu_batch, a.dropout)
         log(f"cpu baseline done: {cpu}")
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Sum the FETCH_SIZE / WRITE_SIZE counters (KB) of the GEMM dispatches issued by `bench.py --ffn-replay N` (they are the
+"""Sum the FETCH_SIZE / WRITE_SIZE counters (KB) of the GEMM dispatches issued by `bench.py --full --ffn-replay N` (they are the
 LAST launches of the run: N x launches_per_step GEMM dispatches, split-K partial reductions in between) -> JSON."""
 import csv
 import glob

@@ -86,3 +86,30 @@ def test_per_rank_batches_differ():
     c0, a0 = make_batch(2, G=8, S=30, seed=1000 + 0)
     c1, a1 = make_batch(2, G=8, S=30, seed=1000 + 1)
     assert not (c0 == c1).all() or not (a0 == a1).all()
+
+
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """`--dump-outputs DIR` (CPU emulation, one process): the last timed step's loss dict, gradient and parameter sample as
+    float32 .npy files under 64 MB, bit-identical between two runs with the same arguments (fixed inputs and seeds)"""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(DSVG_BENCH_EMULATE="1", PYTHONDONTWRITEBYTECODE="1", OMP_NUM_THREADS="2",
+               PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    dumps = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "3",
+               "--batches", "2", "--dtype", "fp32", "--dump-outputs", str(tmp_path / run)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1 and json.loads(lines[0])["steps"] == 2, out.stdout
+        d = tmp_path / run
+        files = sorted(os.listdir(d))
+        assert {"loss.npy", "loss_cmd.npy", "loss_args.npy", "grad.npy", "params_sample.npy"} <= set(files), files
+        assert sum(os.path.getsize(d / f) for f in files) < 64 << 20
+        dumps.append({f: np.load(d / f) for f in files})
+    assert sorted(dumps[0]) == sorted(dumps[1])
+    for f, v in dumps[0].items():
+        assert v.dtype == np.float32 and np.isfinite(v).all(), f
+        assert np.array_equal(v, dumps[1][f]), f
+    assert np.abs(dumps[0]["grad.npy"]).max() > 0

@@ -1,4 +1,5 @@
-"""bench.py honours the driver's contract: one JSON line with the required keys, the roofline and cpu_baseline objects."""
+"""bench.py honours the driver's contract: one JSON line with the required keys; with --full also the roofline and cpu_baseline
+objects; a plain run times the step only and --dump-outputs writes what its last step computed."""
 import json
 import os
 import subprocess
@@ -12,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_json_contract(gpu_device):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "32",
-           "--cpu-batch", "2", "--batches", "3"]
+           "--cpu-batch", "2", "--batches", "3", "--full"]
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -55,6 +56,31 @@ def test_bench_json_contract(gpu_device):
     t = rec["torch_rocm_reference"]
     assert t["ms_per_step"] > 0 and t["dtype"] == "fp32" and t["batch"] == 32
     assert "timed_in" in r
+
+
+def test_bench_plain_run_and_dump_outputs(gpu_device, tmp_path):
+    """the plain command (no --full): the headline line with every extra leg left out, exactly --steps timed steps, and
+    --dump-outputs writing the last timed step's loss dict, gradient and parameter sample as float32 (< 64 MB)"""
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--batch", "32",
+           "--batches", "3", "--dump-outputs", str(tmp_path / "out")]
+    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 4 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["dtype"] == "bf16"
+    assert abs(rec["value"] - 32 / (rec["ms_per_step"] * 1e-3)) < 0.01 * rec["value"]
+    assert "timed 4 steps" in out.stderr
+    for k in ("roofline", "fp32", "dense_layout", "secondary", "in_kernel_clock", "torch_rocm_reference", "cpu_baseline", "ddp"):
+        assert rec[k] is None, k
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert {"loss.npy", "loss_cmd.npy", "loss_args.npy", "grad.npy", "params_sample.npy"} <= set(files), files
+    assert sum(os.path.getsize(tmp_path / "out" / f) for f in files) < 64 << 20
+    arrs = {f: np.load(tmp_path / "out" / f) for f in files}
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in arrs.values())
+    assert abs(float(arrs["loss.npy"][0]) - rec["config"]["loss"]) < 1e-3 and np.abs(arrs["grad.npy"]).max() > 0
 
 
 def test_secondary_workloads_perf_guard(gpu_device):
