@@ -35,6 +35,9 @@ FFN_BWD_ORDER = os.environ.get("DSVG_FFN_BWD_ORDER", "1") != "0"
 # ms/step: the extra pass sits on the tail of a one-workgroup-per-CU kernel), so it is opt-in
 FFN_BWD_MASKED = int(os.environ.get("DSVG_FFN_BWD_MASKED", "0"))    # 1: every layer; 2: only layers without a conditioning row
 # (their bcast_add_bwd launch writes the masked copy anyway, BCAST_MASKED)
+# fused-FFN backward: dpre (the gated GEMM) and the linear2 weight gradient from one launch that stages dym / h once
+# (csrc/ffn_bwd_gate.hip; 0: the two launches)
+FFN_GATE_DW2 = os.environ.get("DSVG_FFN_GATE_DW2", "1") != "0"
 
 # the weight-gradient GEMMs of a layer of the 4096-row stages as one grouped launch (DSVG_GROUP_WGRAD=0: one by one)
 GROUP_WGRAD = os.environ.get("DSVG_GROUP_WGRAD", "1") != "0"
@@ -974,9 +977,16 @@ class LayerFn(torch.autograd.Function):
                     # step, where dym already comes from the masked bcast_add_bwd and dpre is read back from the memory-side
                     # cache; removed.  profiles/r04_experimental_ffn_bwd_one.log, r04_experimental_ab.log)
                     dym = dx2_masked if dx2_masked is not None else ops.drop_apply(dx2, p, s0 + 4, rt.seed)
-                    if FFN_BWD_ORDER:
-                        wgrad2(dym, hp)
-                    dpre = ops.gemm(dym, w2p, b_kc=False, gate=hp, gate_scale=inv_keep)
+                    if (FFN_GATE_DW2 and FFN_BWD_ORDER and s2 > 1 and dym.is_cuda and dym.dtype == torch.bfloat16
+                            and dym.is_contiguous() and hp.is_contiguous() and w2p.is_contiguous()):
+                        # both products of the (dym, h) tiles from one staging: dpre bit-identical, G2p / db2 queued as
+                        # wgrad2's split-K slices would be
+                        with rt.deferring():
+                            dpre = ops.ffn_gate_dw2(dym, hp, w2p, inv_keep, g2p, db2, s2)
+                    else:
+                        if FFN_BWD_ORDER:
+                            wgrad2(dym, hp)
+                        dpre = ops.gemm(dym, w2p, b_kc=False, gate=hp, gate_scale=inv_keep)
                     if FFN_BWD_ORDER:
                         wgrad1(dpre, xh)
                     # (the same launch also hands over dx1 with the attention residual's dropout mask replayed on it)

@@ -1283,6 +1283,29 @@ def ffn_bwd_dx(dpre, x, dy, packed_bwd_layer, eps=1e-5, masked=None):
     return dx
 
 
+def ffn_gate_dw2(dym, hp, w2p, gate_scale, g2p, db2, split_k):
+    """dpre = (dym . W2p) gated by hp > 0, x gate_scale (bf16 [rows, 512], what gemm(dym, w2p, b_kc=False, gate=hp) returns)
+    and, from the same staged tiles, G2p = dym^T hp into g2p / db2 = colsum(dym) into db2 (fp32) by split_k slices - queued
+    like gemm(dym, hp, a_kc=False, b_kc=False, out=g2p, split_k=split_k, rowsum=db2) inside a deferral scope (include/dsvg.h)"""
+    _chk(dym, hp, w2p, g2p, db2)
+    T = dym.shape[0]
+    assert dym.dtype == torch.bfloat16 and dym.dim() == 2 and dym.shape[1] == 256 and dym.is_contiguous()
+    assert hp.dtype == dym.dtype and tuple(hp.shape) == (T, 512) and hp.is_contiguous()
+    assert w2p.dtype == dym.dtype and tuple(w2p.shape) == (256, 512) and w2p.is_contiguous()
+    assert g2p.dtype == torch.float32 and g2p.numel() == 131072 and g2p.is_contiguous()
+    assert db2.dtype == torch.float32 and db2.numel() == 256 and db2.is_contiguous()
+    assert split_k > 1
+    L = _l.load()
+    dpre = torch.empty((T, 512), dtype=dym.dtype, device=dym.device)
+    ws = _ws(L.dsvg_gemm_workspace_bytes(256, 512, split_k), dym.device)
+    ev = _prof_begin()
+    _l.check(L.dsvg_ffn_gate_dw2(dym.data_ptr(), hp.data_ptr(), w2p.data_ptr(), float(gate_scale), dpre.data_ptr(), T,
+                                 int(split_k), g2p.data_ptr(), db2.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream()),
+             "dsvg_ffn_gate_dw2")
+    _prof_end(ev, 4.0 * 256 * 512 * T, 2.0 * (256 + 512 + 512) * T, dict(op="ffn_gate_dw2", rows=T))
+    return dpre
+
+
 def ffn_wgrad_finish(g1p, db1p, g2p, w1, gamma, beta, dw1, db1, dw2, dgamma, dbeta):
     """(G1p = dpre^T xh, its row sums, G2p = dym^T h) in fragment order -> gradients of linear1.weight / bias,
     linear2.weight, norm.weight, norm.bias (include/dsvg.h)"""

@@ -38,8 +38,9 @@ extern "C" {
  * 7 (round 6): dsvg_attn_bwd_dx added; a layer of dsvg_attn_pack_bwd grew from 128 to 512 fragments (in_proj_weight^T behind
  *    out_proj.weight^T).
  * 8 (round 6): dsvg_gs_stack_fwd / dsvg_gs_stack_bwd added (one launch per STACK of group-stage layers).
- * 9 (round 6): dg_ld argument of dsvg_bcast_add_bwd / dsvg_bcast_add_bwd_masked (dg as a column block of a wider buffer). */
-#define DSVG_ABI_VERSION 9
+ * 9 (round 6): dg_ld argument of dsvg_bcast_add_bwd / dsvg_bcast_add_bwd_masked (dg as a column block of a wider buffer).
+ * 10: dsvg_ffn_gate_dw2 added (the gated dpre GEMM and the dW2 split-K GEMM of the fused FFN backward as one launch). */
+#define DSVG_ABI_VERSION 10
 
 const char* dsvg_last_error(void);
 int dsvg_version(void);
@@ -554,6 +555,15 @@ int dsvg_ffn_bwd(const void* x, const void* dy, const void* packed_bwd_layer, co
 int dsvg_ffn_bwd_dx(const void* dpre, const void* x, const void* dy, const void* packed_bwd_layer, void* dx,
                     int64_t rows, float eps, void* dx_masked, float drop_p, uint32_t drop_site, const void* seed,
                     void* stream);
+/* dpre and the linear2 weight gradient from one staging of their common operands (csrc/ffn_bwd_gate.hip):
+ *   dpre = (dym . W2p) gated by hp > 0, x gate_scale     (bf16 [rows, 512], bit-identical to the dsvg_gemm with gate = hp)
+ *   G2p = dym^T hp [256, 512] fp32, db2 = colsum(dym) [256] fp32
+ * dym bf16 [rows, 256], hp bf16 [rows, 512] (the h dsvg_ffn_fwd stored), w2p bf16 [256, 512] (the packed W2 dsvg_gemm reads
+ * with b_kc = 0); all row-major and dense.  G2p / db2 come as split_k (> 1) slices in the layout of dsvg_gemm(dym, hp, a_kc =
+ * b_kc = 0, split_k, rowsum = db2) - workspace of dsvg_gemm_workspace_bytes(256, 512, split_k) - and are reduced the same way:
+ * queued inside an open dsvg_defer_scope, valid after dsvg_flush_deferred. */
+int dsvg_ffn_gate_dw2(const void* dym, const void* hp, const void* w2p, float gate_scale, void* dpre, int64_t rows,
+                      int32_t split_k, float* g2p, float* db2, float* workspace, int64_t workspace_bytes, void* stream);
 int dsvg_ffn_wgrad_finish(const float* g1p, const float* db1p, const float* g2p, const float* w1, const float* gamma,
                           const float* beta, float* dw1, float* db1, float* dw2, float* dgamma, float* dbeta,
                           void* stream);
