@@ -232,6 +232,46 @@ extern "C" int dsvg_pack_tokens(const float* commands, const float* args, const 
     return 0;
 }
 
+// The same layout for paths of up to 256 tokens, from the valid-prefix lengths of dsvg_build_masks_lens
+__global__ __launch_bounds__(1024) void seq_offsets_lens_kernel(const int32_t* __restrict__ lens, long long n_seq, int S,
+                                                                int32_t* __restrict__ seq_off) {
+    __shared__ int part[1024];
+    __shared__ int carry;
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    for (long long base = 0; base < n_seq; base += 1024) {
+        const long long b = base + threadIdx.x;
+        const int len = b < n_seq ? min(max(lens[b], 0), S) : 0;
+        part[threadIdx.x] = len;
+        __syncthreads();
+        for (int o = 1; o < 1024; o <<= 1) {
+            const int v = threadIdx.x >= o ? part[threadIdx.x - o] : 0;
+            __syncthreads();
+            part[threadIdx.x] += v;
+            __syncthreads();
+        }
+        if (b < n_seq) seq_off[b] = carry + part[threadIdx.x] - len;
+        __syncthreads();
+        if (threadIdx.x == 1023) carry += part[1023];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) seq_off[n_seq] = carry;
+}
+extern "C" int dsvg_pack_tokens_lens(const float* commands, const float* args, const int32_t* lens, int64_t n_seq,
+                                     int32_t S, int32_t n_args, int32_t* seq_off, float* packed_commands,
+                                     float* packed_args, int32_t* packed_pos, void* stream) {
+    DSVG_CHECK_ARG(commands && args && lens && seq_off && packed_commands && packed_args && packed_pos,
+                   "pack_tokens_lens: null pointer");
+    DSVG_CHECK_ARG(n_seq > 0 && S > 0 && S <= 256 && n_args > 0 && n_seq * S < (1ll << 31), "pack_tokens_lens: bad shape");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(seq_offsets_lens_kernel, dim3(1), dim3(1024), 0, st, lens, (long long)n_seq, S, seq_off);
+    DSVG_LAUNCH_CHECK("seq_offsets_lens");
+    hipLaunchKernelGGL(pack_tokens_kernel, dim3(dsvg_cdiv(n_seq * S, 256)), dim3(256), 0, st, commands, args, seq_off,
+                       (long long)n_seq, S, n_args, packed_commands, packed_args, packed_pos);
+    DSVG_LAUNCH_CHECK("pack_tokens_lens");
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // embedding gather (deepsvg/model/model.py:49-53)
 //   A[t, a*E + e] = arg_embed[args[t,a] + 1, e];   R[t, c] = command_embed[cmd[t], c] (+ group_embed[grp[t], c])

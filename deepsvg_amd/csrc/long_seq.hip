@@ -26,23 +26,45 @@ __device__ __forceinline__ void stage_slab(float* dst, const T* __restrict__ src
     }
 }
 
+// rows [first, total_rows) of head h's 32 columns <- 0 (packed layout: the rows behind the last sequence)
 template <typename T>
+__device__ __forceinline__ void zero_tail_rows(T* dst, long long ld, long long first, long long total_rows) {
+    for (long long idx = threadIdx.x; idx < (total_rows - first) * 32; idx += AL_THREADS)
+        Elem<T>::st(dst + (first + (idx >> 5)) * ld + (idx & 31), 0.f);
+}
+
+// PACKED: the packed layout of dsvg_pack_tokens_lens (sequence b = rows seq_off[b] .. seq_off[b+1] - 1, every row a valid
+// query and key); one more workgroup per head zero-fills the rows [seq_off[n_seq], total_rows).  Dropout rows keep the
+// padded numbering (b H + h) S + i, so both layouts draw the same mask.
+template <typename T, bool PACKED>
 __global__ __launch_bounds__(AL_THREADS) void attn_long_fwd_kernel(const T* __restrict__ qkv,
                                                                    const int32_t* __restrict__ seq_len,
                                                                    T* __restrict__ out, int S, int H, float scale,
                                                                    int causal, float drop_p, uint32_t site,
-                                                                   const uint64_t* seed) {
+                                                                   const uint64_t* seed, const int32_t* __restrict__ seq_off,
+                                                                   long long total_rows) {
     extern __shared__ float sm[];
     float* Ks = sm;
     float* Vs = sm + S * AL_LD;
     const int b = blockIdx.x, h = blockIdx.y, d = H * 32;
-    const T* base = qkv + (size_t)b * S * 3 * d + h * 32;
-    stage_slab<T>(Ks, base + d, 3LL * d, S);
-    stage_slab<T>(Vs, base + 2 * d, 3LL * d, S);
+    long long row0 = (long long)b * S;
+    int nq = S, len;
+    if (PACKED) {
+        if (b == (int)gridDim.x - 1) {
+            zero_tail_rows<T>(out + h * 32, d, seq_off[b], total_rows);
+            return;
+        }
+        row0 = seq_off[b];
+        len = nq = min(seq_off[b + 1] - seq_off[b], S);      // (<= S by construction: LDS holds S rows)
+    } else {
+        len = seq_len ? min(max(seq_len[b], 0), S) : S;
+    }
+    const T* base = qkv + (size_t)row0 * 3 * d + h * 32;
+    stage_slab<T>(Ks, base + d, 3LL * d, nq);
+    stage_slab<T>(Vs, base + 2 * d, 3LL * d, nq);
     __syncthreads();
-    const int len = seq_len ? min(max(seq_len[b], 0), S) : S;
     const DropCtx dc = drop_make(drop_p, seed, site);
-    for (int i = threadIdx.x; i < S; i += AL_THREADS) {
+    for (int i = threadIdx.x; i < nq; i += AL_THREADS) {
         float q[32], o[32];
 #pragma unroll
         for (int c = 0; c < 32; ++c) { q[c] = Elem<T>::ld(base + (size_t)i * 3 * d + c) * scale; o[c] = 0.f; }
@@ -66,7 +88,7 @@ __global__ __launch_bounds__(AL_THREADS) void attn_long_fwd_kernel(const T* __re
             m = mn;
         }
         const float inv = jend > 0 ? 1.f / l : 0.f;
-        T* dst = out + ((size_t)b * S + i) * d + h * 32;
+        T* dst = out + ((size_t)row0 + i) * d + h * 32;
 #pragma unroll
         for (int c = 0; c < 32; ++c) Elem<T>::st(dst + c, o[c] * inv);
     }
@@ -142,12 +164,13 @@ __global__ __launch_bounds__(AL_THREADS) void attn_long_row_kernel(const T* __re
     }
 }
 
-template <typename T>
+template <typename T, bool PACKED>
 __global__ __launch_bounds__(AL_THREADS) void attn_long_bwd_kernel(const T* __restrict__ qkv,
                                                                    const int32_t* __restrict__ seq_len,
                                                                    const T* __restrict__ dout, T* __restrict__ dqkv,
                                                                    int S, int H, float scale, int causal, float drop_p,
-                                                                   uint32_t site, const uint64_t* seed) {
+                                                                   uint32_t site, const uint64_t* seed,
+                                                                   const int32_t* __restrict__ seq_off, long long total_rows) {
     extern __shared__ float sm[];
     float* Qs = sm;
     float* Ks = Qs + S * AL_LD;
@@ -156,19 +179,30 @@ __global__ __launch_bounds__(AL_THREADS) void attn_long_bwd_kernel(const T* __re
     float* lse_s = Gs + S * AL_LD;
     float* D_s = lse_s + S;
     const int b = blockIdx.x, h = blockIdx.y, d = H * 32;
-    const T* base = qkv + (size_t)b * S * 3 * d + h * 32;
-    stage_slab<T>(Qs, base, 3LL * d, S);
-    stage_slab<T>(Ks, base + d, 3LL * d, S);
-    stage_slab<T>(Vs, base + 2 * d, 3LL * d, S);
-    stage_slab<T>(Gs, dout + (size_t)b * S * d + h * 32, (long long)d, S);
+    long long row0 = (long long)b * S;
+    int nq = S, len;
+    if (PACKED) {       // (see the forward kernel)
+        if (b == (int)gridDim.x - 1) {
+            for (int k = 0; k < 3; ++k) zero_tail_rows<T>(dqkv + k * d + h * 32, 3LL * d, seq_off[b], total_rows);
+            return;
+        }
+        row0 = seq_off[b];
+        len = nq = min(seq_off[b + 1] - seq_off[b], S);      // (<= S by construction: LDS holds S rows)
+    } else {
+        len = seq_len ? min(max(seq_len[b], 0), S) : S;
+    }
+    const T* base = qkv + (size_t)row0 * 3 * d + h * 32;
+    stage_slab<T>(Qs, base, 3LL * d, nq);
+    stage_slab<T>(Ks, base + d, 3LL * d, nq);
+    stage_slab<T>(Vs, base + 2 * d, 3LL * d, nq);
+    stage_slab<T>(Gs, dout + (size_t)row0 * d + h * 32, (long long)d, nq);
     __syncthreads();
-    const int len = seq_len ? min(max(seq_len[b], 0), S) : S;
     const DropCtx dc = drop_make(drop_p, seed, site);
     const uint64_t hbase = ((uint64_t)b * H + h) * S;       // dropout row of query i = hbase + i
-    T* dbase = dqkv + (size_t)b * S * 3 * d + h * 32;
+    T* dbase = dqkv + (size_t)row0 * 3 * d + h * 32;
 
     // ---- pass 1: lane = query row i: lse_i, D_i = sum_j P_ij dP_ij, dq_i ---------------------------------------
-    for (int i = threadIdx.x; i < S; i += AL_THREADS) {
+    for (int i = threadIdx.x; i < nq; i += AL_THREADS) {
         float q[32], go[32];
 #pragma unroll
         for (int c = 0; c < 32; ++c) { q[c] = Qs[i * AL_LD + c] * scale; go[c] = Gs[i * AL_LD + c]; }
@@ -211,7 +245,7 @@ __global__ __launch_bounds__(AL_THREADS) void attn_long_bwd_kernel(const T* __re
     __syncthreads();
 
     // ---- pass 2: lane = key row j: dk_j, dv_j over the query rows that see it ---------------------------------------
-    for (int j = threadIdx.x; j < S; j += AL_THREADS) {
+    for (int j = threadIdx.x; j < nq; j += AL_THREADS) {
         float dk[32], dv[32];
 #pragma unroll
         for (int c = 0; c < 32; ++c) { dk[c] = 0.f; dv[c] = 0.f; }
@@ -219,7 +253,7 @@ __global__ __launch_bounds__(AL_THREADS) void attn_long_bwd_kernel(const T* __re
             float k[32], v[32];
 #pragma unroll
             for (int c = 0; c < 32; ++c) { k[c] = Ks[j * AL_LD + c]; v[c] = Vs[j * AL_LD + c]; }
-            for (int r = causal ? j : 0; r < S; ++r) {
+            for (int r = causal ? j : 0; r < nq; ++r) {
                 const float* qr = Qs + r * AL_LD;
                 const float* gr = Gs + r * AL_LD;
                 float s = 0.f, dpv = 0.f;
@@ -275,6 +309,66 @@ __global__ void prefix_mean_bwd_kernel(const T* __restrict__ dout, const int32_t
         for (int i = 0; i < S; ++i, px += d) Elem<T>::st(px, i < len ? g : 0.f);
     }
 }
+// Two-stage configs with paths of 65..256 tokens (the masks of dsvg_build_masks as lengths): lens[b] = first-EOS index,
+// seq_visible[b] = (number of EOS tokens < S - 1), the rule of dsvg_build_masks (deepsvg/model/model.py:128-131)
+__global__ void masks_lens_kernel(const float* __restrict__ commands, long long n_seq, int S, int eos,
+                                  int32_t* __restrict__ lens, int32_t* __restrict__ seq_visible) {
+    const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n_seq) return;
+    const float* row = commands + b * S;
+    int fe = S, n_eos = 0;
+    for (int s = S - 1; s >= 0; --s) {
+        const bool is_eos = ((int)row[s] == eos);
+        n_eos += is_eos;
+        if (is_eos) fe = s;
+    }
+    lens[b] = fe;
+    if (seq_visible) seq_visible[b] = (n_eos < S - 1) ? 1 : 0;
+}
+__global__ void group_bits_kernel(const int32_t* __restrict__ seq_visible, long long n_icons, int G,
+                                  uint64_t* __restrict__ group_mask) {
+    const long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= n_icons) return;
+    uint64_t gm = 0;
+    for (int g = 0; g < G; ++g)
+        if (seq_visible[n * G + g]) gm |= (1ull << g);
+    group_mask[n] = gm;
+}
+
+// mean over the rows of each packed sequence (seq_off) and its backward; the backward's extra workgroup zero-fills the rows
+// [seq_off[n_seq], total_rows) behind the last sequence.  0 rows: 0/0, like the reference (model.py:137)
+template <typename T>
+__global__ void packed_mean_fwd_kernel(const T* __restrict__ x, const int32_t* __restrict__ seq_off, T* __restrict__ out,
+                                       int d) {
+    const long long b = blockIdx.x;
+    const long long row0 = seq_off[b];
+    const int len = seq_off[b + 1] - seq_off[b];
+    const float inv = 1.f / (float)len;
+    for (int c = threadIdx.x; c < d; c += blockDim.x) {
+        float s = 0.f;
+        const T* px = x + row0 * d + c;
+        for (int i = 0; i < len; ++i, px += d) s += Elem<T>::ld(px);
+        Elem<T>::st(out + b * d + c, s * inv);
+    }
+}
+template <typename T>
+__global__ void packed_mean_bwd_kernel(const T* __restrict__ dout, const int32_t* __restrict__ seq_off,
+                                       long long total_rows, T* __restrict__ dx, int d) {
+    const long long b = blockIdx.x;
+    if (b == (long long)gridDim.x - 1) {
+        for (long long i = (long long)seq_off[b] * d + threadIdx.x; i < total_rows * d; i += blockDim.x)
+            Elem<T>::st(dx + i, 0.f);
+        return;
+    }
+    const long long row0 = seq_off[b];
+    const int len = seq_off[b + 1] - seq_off[b];
+    const float inv = 1.f / (float)len;
+    for (int c = threadIdx.x; c < d; c += blockDim.x) {
+        const float g = Elem<T>::ld(dout + b * d + c) * inv;
+        T* px = dx + row0 * d + c;
+        for (int i = 0; i < len; ++i, px += d) Elem<T>::st(px, g);
+    }
+}
 }  // namespace
 
 extern "C" int dsvg_seq_lens(const float* commands, int64_t n_seq, int32_t S, int32_t eos_id, int32_t* lens,
@@ -313,15 +407,15 @@ extern "C" int dsvg_attention_long_fwd(int32_t dtype, const void* qkv, const int
     }
     const size_t lds = (size_t)2 * S * AL_LD * sizeof(float);
     if (dtype == DSVG_F32) {
-        auto kern = attn_long_fwd_kernel<float>;
+        auto kern = attn_long_fwd_kernel<float, false>;
         DSVG_ENSURE_LDS(kern, lds);
         hipLaunchKernelGGL(kern, grid, dim3(AL_THREADS), lds, st, (const float*)qkv, seq_len, (float*)out, S, n_heads, scale,
-                           causal, drop_p, drop_site, seed);
+                           causal, drop_p, drop_site, seed, nullptr, 0LL);
     } else if (dtype == DSVG_BF16) {
-        auto kern = attn_long_fwd_kernel<bf16_t>;
+        auto kern = attn_long_fwd_kernel<bf16_t, false>;
         DSVG_ENSURE_LDS(kern, lds);
         hipLaunchKernelGGL(kern, grid, dim3(AL_THREADS), lds, st, (const bf16_t*)qkv, seq_len, (bf16_t*)out, S, n_heads,
-                           scale, causal, drop_p, drop_site, seed);
+                           scale, causal, drop_p, drop_site, seed, nullptr, 0LL);
     } else { dsvg_set_error("attention_long_fwd: bad dtype"); return -1; }
     DSVG_LAUNCH_CHECK("attention_long_fwd");
     return 0;
@@ -337,15 +431,15 @@ extern "C" int dsvg_attention_long_bwd(int32_t dtype, const void* qkv, const int
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)n_seq, (unsigned)n_heads);
     if (dtype == DSVG_F32) {
-        auto kern = attn_long_bwd_kernel<float>;
+        auto kern = attn_long_bwd_kernel<float, false>;
         DSVG_ENSURE_LDS(kern, lds);
         hipLaunchKernelGGL(kern, grid, dim3(AL_THREADS), lds, st, (const float*)qkv, seq_len, (const float*)dout,
-                           (float*)dqkv, S, n_heads, scale, causal, drop_p, drop_site, seed);
+                           (float*)dqkv, S, n_heads, scale, causal, drop_p, drop_site, seed, nullptr, 0LL);
     } else if (dtype == DSVG_BF16) {
-        auto kern = attn_long_bwd_kernel<bf16_t>;
+        auto kern = attn_long_bwd_kernel<bf16_t, false>;
         DSVG_ENSURE_LDS(kern, lds);
         hipLaunchKernelGGL(kern, grid, dim3(AL_THREADS), lds, st, (const bf16_t*)qkv, seq_len, (const bf16_t*)dout,
-                           (bf16_t*)dqkv, S, n_heads, scale, causal, drop_p, drop_site, seed);
+                           (bf16_t*)dqkv, S, n_heads, scale, causal, drop_p, drop_site, seed, nullptr, 0LL);
     } else { dsvg_set_error("attention_long_bwd: bad dtype"); return -1; }
     DSVG_LAUNCH_CHECK("attention_long_bwd");
     return 0;
@@ -377,5 +471,100 @@ extern "C" int dsvg_prefix_mean_bwd(int32_t dtype, const void* dout, const int32
                            (bf16_t*)dx, S, d);
     else { dsvg_set_error("prefix_mean_bwd: bad dtype"); return -1; }
     DSVG_LAUNCH_CHECK("prefix_mean_bwd");
+    return 0;
+}
+
+extern "C" int dsvg_build_masks_lens(const float* commands, int64_t n_seq, int32_t S, int32_t G, int32_t eos_id,
+                                     int32_t* lens, int32_t* seq_visible, uint64_t* group_mask, void* stream) {
+    DSVG_CHECK_ARG(commands && lens && n_seq > 0 && S > 0 && S <= AL_MAX_S, "build_masks_lens: bad args (S=%d)", S);
+    DSVG_CHECK_ARG(!group_mask || (seq_visible && G > 0 && G <= 64 && n_seq % G == 0), "build_masks_lens: bad group args");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(masks_lens_kernel, dim3((unsigned)dsvg_cdiv(n_seq, 256)), dim3(256), 0, st, commands,
+                       (long long)n_seq, S, eos_id, lens, seq_visible);
+    DSVG_LAUNCH_CHECK("build_masks_lens");
+    if (group_mask) {
+        hipLaunchKernelGGL(group_bits_kernel, dim3((unsigned)dsvg_cdiv(n_seq / G, 256)), dim3(256), 0, st, seq_visible,
+                           (long long)(n_seq / G), G, group_mask);
+        DSVG_LAUNCH_CHECK("build_masks_lens (group mask)");
+    }
+    return 0;
+}
+
+extern "C" int dsvg_packed_mean_fwd(int32_t dtype, const void* x, const int32_t* seq_off, void* out, int64_t n_seq,
+                                    int32_t d, void* stream) {
+    DSVG_CHECK_ARG(x && seq_off && out && n_seq > 0 && d > 0, "packed_mean_fwd: bad args");
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == DSVG_F32)
+        hipLaunchKernelGGL(packed_mean_fwd_kernel<float>, dim3((unsigned)n_seq), dim3(256), 0, st, (const float*)x, seq_off,
+                           (float*)out, d);
+    else if (dtype == DSVG_BF16)
+        hipLaunchKernelGGL(packed_mean_fwd_kernel<bf16_t>, dim3((unsigned)n_seq), dim3(256), 0, st, (const bf16_t*)x, seq_off,
+                           (bf16_t*)out, d);
+    else { dsvg_set_error("packed_mean_fwd: bad dtype"); return -1; }
+    DSVG_LAUNCH_CHECK("packed_mean_fwd");
+    return 0;
+}
+extern "C" int dsvg_packed_mean_bwd(int32_t dtype, const void* dout, const int32_t* seq_off, int64_t total_rows, void* dx,
+                                    int64_t n_seq, int32_t d, void* stream) {
+    DSVG_CHECK_ARG(dout && seq_off && dx && n_seq > 0 && d > 0 && total_rows >= 0, "packed_mean_bwd: bad args");
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == DSVG_F32)
+        hipLaunchKernelGGL(packed_mean_bwd_kernel<float>, dim3((unsigned)n_seq + 1u), dim3(256), 0, st, (const float*)dout,
+                           seq_off, (long long)total_rows, (float*)dx, d);
+    else if (dtype == DSVG_BF16)
+        hipLaunchKernelGGL(packed_mean_bwd_kernel<bf16_t>, dim3((unsigned)n_seq + 1u), dim3(256), 0, st, (const bf16_t*)dout,
+                           seq_off, (long long)total_rows, (bf16_t*)dx, d);
+    else { dsvg_set_error("packed_mean_bwd: bad dtype"); return -1; }
+    DSVG_LAUNCH_CHECK("packed_mean_bwd");
+    return 0;
+}
+
+// the VALU long kernels on the packed layout (fp32 parity path; bf16 runs dsvg_attention_long_mfma_*)
+extern "C" int dsvg_attention_long_packed_fwd(int32_t dtype, const void* qkv, const int32_t* seq_off, int64_t total_rows,
+                                              void* out, int64_t n_seq, int32_t S, int32_t n_heads, float scale,
+                                              float drop_p, uint32_t drop_site, const uint64_t* seed, void* stream) {
+    DSVG_CHECK_ARG(qkv && seq_off && out && n_seq > 0 && S > 0 && S <= AL_MAX_S && n_heads > 0 && n_seq < (1ll << 31) &&
+                   total_rows > 0, "attention_long_packed_fwd: bad args (S=%d, at most %d)", S, AL_MAX_S);
+    DSVG_CHECK_ARG(drop_p <= 0.f || seed, "attention_long_packed_fwd: dropout needs a seed pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)n_seq + 1u, (unsigned)n_heads);
+    const size_t lds = (size_t)2 * S * AL_LD * sizeof(float);
+    if (dtype == DSVG_F32) {
+        auto kern = attn_long_fwd_kernel<float, true>;
+        DSVG_ENSURE_LDS(kern, lds);
+        hipLaunchKernelGGL(kern, grid, dim3(AL_THREADS), lds, st, (const float*)qkv, nullptr, (float*)out, S, n_heads, scale,
+                           0, drop_p, drop_site, seed, seq_off, (long long)total_rows);
+    } else if (dtype == DSVG_BF16) {
+        auto kern = attn_long_fwd_kernel<bf16_t, true>;
+        DSVG_ENSURE_LDS(kern, lds);
+        hipLaunchKernelGGL(kern, grid, dim3(AL_THREADS), lds, st, (const bf16_t*)qkv, nullptr, (bf16_t*)out, S, n_heads,
+                           scale, 0, drop_p, drop_site, seed, seq_off, (long long)total_rows);
+    } else { dsvg_set_error("attention_long_packed_fwd: bad dtype"); return -1; }
+    DSVG_LAUNCH_CHECK("attention_long_packed_fwd");
+    return 0;
+}
+extern "C" int dsvg_attention_long_packed_bwd(int32_t dtype, const void* qkv, const int32_t* seq_off, int64_t total_rows,
+                                              const void* dout, void* dqkv, int64_t n_seq, int32_t S, int32_t n_heads,
+                                              float scale, float drop_p, uint32_t drop_site, const uint64_t* seed,
+                                              void* stream) {
+    DSVG_CHECK_ARG(qkv && seq_off && dout && dqkv && n_seq > 0 && S > 0 && S <= AL_MAX_S && n_heads > 0 &&
+                   n_seq < (1ll << 31) && total_rows > 0, "attention_long_packed_bwd: bad args (S=%d, at most %d)", S,
+                   AL_MAX_S);
+    DSVG_CHECK_ARG(drop_p <= 0.f || seed, "attention_long_packed_bwd: dropout needs a seed pointer");
+    const size_t lds = ((size_t)4 * S * AL_LD + 2 * S) * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)n_seq + 1u, (unsigned)n_heads);
+    if (dtype == DSVG_F32) {
+        auto kern = attn_long_bwd_kernel<float, true>;
+        DSVG_ENSURE_LDS(kern, lds);
+        hipLaunchKernelGGL(kern, grid, dim3(AL_THREADS), lds, st, (const float*)qkv, nullptr, (const float*)dout,
+                           (float*)dqkv, S, n_heads, scale, 0, drop_p, drop_site, seed, seq_off, (long long)total_rows);
+    } else if (dtype == DSVG_BF16) {
+        auto kern = attn_long_bwd_kernel<bf16_t, true>;
+        DSVG_ENSURE_LDS(kern, lds);
+        hipLaunchKernelGGL(kern, grid, dim3(AL_THREADS), lds, st, (const bf16_t*)qkv, nullptr, (const bf16_t*)dout,
+                           (bf16_t*)dqkv, S, n_heads, scale, 0, drop_p, drop_site, seed, seq_off, (long long)total_rows);
+    } else { dsvg_set_error("attention_long_packed_bwd: bad dtype"); return -1; }
+    DSVG_LAUNCH_CHECK("attention_long_packed_bwd");
     return 0;
 }

@@ -100,6 +100,8 @@ class Runtime:
         self.masked = {}
         self.last_layer_gs = False
         self.stack_group = None
+        # a two-stage model: its sequences of more than 64 tokens are paths (ops.attention_fwd / bwd path_stage)
+        self.path_stage = False
         # base address of a stack's projected conditioning rows (GlobalCondFn's [n_seq, n * 256] product) -> the buffer its layers'
         # backward passes write their gradients into, side by side (COND_GRAD_SHARED)
         self.cond_grad = {}
@@ -446,6 +448,11 @@ class AddPosFn(torch.autograd.Function):
             dx = ops.add_pos_bwd(dy, n_seq, ctx.S, dpos[:ctx.S], want_dx=ctx.has_x, drop_p=ctx.p,
                                  drop_site=ctx.site, seed=rt.seed)
         return None, dx, dpos, None, None, None, None, None
+
+
+def _path_kw(rt, S):
+    """the path-stage flag of ops.attention_fwd / bwd, passed for the sequences it concerns only"""
+    return {"path_stage": True} if (rt.path_stage and S > 64) else {}
 
 
 class MaskedMeanFn(torch.autograd.Function):
@@ -836,7 +843,7 @@ class LayerFn(torch.autograd.Function):
                 ao = ops.attention_fwd(qkv, key_mask, n_seq, S, n_heads, scale, p, site0, rt.seed, causal=True)
             else:
                 ao = ops.attention_fwd(qkv, key_mask, n_seq, S, n_heads, scale, p, site0, rt.seed, seq_off=seq_off,
-                                       tiles=tiles)
+                                       tiles=tiles, **_path_kw(rt, S))
             x1 = ops.gemm(ao, rt.w(wo), bias=bo.detach(), res=x, drop_p=p, drop_site=site0 + 1, seed=rt.seed)
         ctx.tiles, ctx.causal = tiles, causal
         if z is not None and not z_fused:
@@ -1064,7 +1071,7 @@ class LayerFn(torch.autograd.Function):
                 dqkv = ops.attention_bwd(qkv, key_mask, dao, n_seq, S, H, ctx.scale, p, s0, rt.seed, causal=True)
             else:
                 dqkv = ops.attention_bwd(qkv, key_mask, dao, n_seq, S, H, ctx.scale, p, s0, rt.seed, seq_off=seq_off,
-                                         tiles=ctx.tiles)
+                                         tiles=ctx.tiles, **_path_kw(rt, S))
         del dx1m
         dwin, dbin = _wbgrad(rt, win, bin_, dqkv, xn1)
         dx_out = None

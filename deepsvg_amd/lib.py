@@ -14,7 +14,7 @@ DSVG_F32 = 0
 DSVG_BF16 = 1
 # == DSVG_ABI_VERSION of include/dsvg.h at the time SIGNATURES below was written: load() refuses a library built from another
 # header (a stale .so with the old argument lists would otherwise be called with a stream where a size is expected)
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 c_i32, c_i64, c_u32, c_f32 = C.c_int32, C.c_int64, C.c_uint32, C.c_float
 vp = C.c_void_p
@@ -135,6 +135,17 @@ SIGNATURES = {
     "dsvg_attention_long_bwd": (c_i32, [c_i32, vp, vp, vp, vp, c_i64, c_i32, c_i32, c_f32, c_i32, c_f32, c_u32, vp, vp]),
     "dsvg_prefix_mean_fwd": (c_i32, [c_i32, vp, vp, vp, c_i64, c_i32, c_i32, vp]),
     "dsvg_prefix_mean_bwd": (c_i32, [c_i32, vp, vp, vp, c_i64, c_i32, c_i32, vp]),
+    "dsvg_build_masks_lens": (c_i32, [vp, c_i64, c_i32, c_i32, c_i32, vp, vp, vp, vp]),
+    "dsvg_pack_tokens_lens": (c_i32, [vp, vp, vp, c_i64, c_i32, c_i32, vp, vp, vp, vp, vp]),
+    "dsvg_packed_mean_fwd": (c_i32, [c_i32, vp, vp, vp, c_i64, c_i32, vp]),
+    "dsvg_packed_mean_bwd": (c_i32, [c_i32, vp, vp, c_i64, vp, c_i64, c_i32, vp]),
+    "dsvg_attention_long_packed_fwd": (c_i32, [c_i32, vp, vp, c_i64, vp, c_i64, c_i32, c_i32, c_f32, c_f32, c_u32, vp,
+                                               vp]),
+    "dsvg_attention_long_packed_bwd": (c_i32, [c_i32, vp, vp, c_i64, vp, vp, c_i64, c_i32, c_i32, c_f32, c_f32, c_u32,
+                                               vp, vp]),
+    "dsvg_attention_long_mfma_fwd": (c_i32, [vp, vp, vp, c_i64, vp, c_i64, c_i32, c_i32, c_f32, c_f32, c_u32, vp, vp]),
+    "dsvg_attention_long_mfma_bwd": (c_i32, [vp, vp, vp, c_i64, vp, vp, c_i64, c_i32, c_i32, c_f32, c_f32, c_u32, vp,
+                                             vp]),
     "dsvg_match_costs": (c_i32, [c_i32, vp, c_i64, vp, c_i64, vp, c_i64, vp, vp, vp, c_i64, c_i32, c_i32, c_i32, c_i32,
                                  c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, vp, vp, vp]),
     "dsvg_match_assign": (c_i32, [vp, vp, c_i64, c_i32, c_i32, vp, vp, vp, vp]),

@@ -608,8 +608,10 @@ class SVGTransformer(nn.Module):
         if longest > 256:
             raise NotImplementedError(f"sequences of {longest} tokens: the long-sequence attention kernel holds one "
                                       "sequence per workgroup in LDS, at most 256 tokens")
-        if (cfg.encode_stages == 2 or cfg.decode_stages == 2) and cfg.max_seq_len + 2 > 64:
-            raise NotImplementedError("two-stage configs are built for groups of at most 62 commands")
+        # (two-stage configs: paths of up to 254 commands, max_seq_len + 2 <= 256, by the check above)
+        if (cfg.encode_stages == 2 or cfg.decode_stages == 2) and cfg.self_match and cfg.max_seq_len + 2 > 64:
+            raise NotImplementedError("self-matching configs are built for paths of at most 62 commands: the Hungarian cost "
+                                      "kernel (csrc/match.hip, dsvg_match_costs) holds a path in one 64-bit word")
         if cfg.d_model // cfg.n_heads != 32 or cfg.d_model % cfg.n_heads:
             raise NotImplementedError("the attention kernel is specialised for head_dim == 32")
         self.args_dim = 2 * cfg.args_dim if cfg.rel_targets else cfg.args_dim + 1
@@ -690,6 +692,7 @@ class SVGTransformer(nn.Module):
         self._store.ensure(device, self.compute_dtype, advance=(None, seed) if training and self._own_seed else None)
         self._rt = Fn.Runtime(self.compute_dtype, seed, self._store, training,
                               defer=self._defer_wgrad and (not ops.PROFILE_ON or ops.PROFILE_KEEP_DEFER))
+        self._rt.path_stage = self.cfg.encode_stages == 2 or self.cfg.decode_stages == 2
         return self._rt
 
     # ---- blocks ----------------------------------------------------------------------------------
@@ -768,8 +771,12 @@ class SVGTransformer(nn.Module):
             N, G, S = commands_enc.shape
             cmd = commands_enc.to(torch.float32).contiguous().view(N * G, S)
             arg = args_enc.to(torch.float32).contiguous().view(N * G * S, -1)
-            key_mask, _vis, group_mask = ops.build_masks(cmd, S, G, EOS_ID, want_group_mask=cfg.encode_stages == 2)
-            seq_off, pcmd, parg, ppos = ops.pack_tokens(cmd.view(-1), arg, key_mask, N * G, S)
+            if S > 64 and cfg.encode_stages == 2:       # paths of 65..256 tokens: valid-prefix lengths
+                key_mask, _vis, group_mask = ops.build_masks_lens(cmd, S, G, EOS_ID, want_group_mask=True)
+                seq_off, pcmd, parg, ppos = ops.pack_tokens_lens(cmd.view(-1), arg, key_mask, N * G, S)
+            else:
+                key_mask, _vis, group_mask = ops.build_masks(cmd, S, G, EOS_ID, want_group_mask=cfg.encode_stages == 2)
+                seq_off, pcmd, parg, ppos = ops.pack_tokens(cmd.view(-1), arg, key_mask, N * G, S)
             tiles = ops.attention_tiles(seq_off, N * G, 32) if S <= 32 else None
             plan["enc"] = dict(key_mask=key_mask, group_mask=group_mask, seq_off=seq_off, pcmd=pcmd, parg=parg, ppos=ppos,
                                tiles=tiles)
@@ -779,7 +786,7 @@ class SVGTransformer(nn.Module):
                 and not cfg.self_match):        # (self-matching pairs predictions with targets only after the forward)
             N, G, St = commands_dec.shape
             cmd_t = commands_dec.to(torch.float32).contiguous().view(N * G, St)
-            _km, vis, _gm = ops.build_masks(cmd_t, St, G, EOS_ID)
+            _km, vis, _gm = (ops.build_masks_lens if St > 64 else ops.build_masks)(cmd_t, St, G, EOS_ID)
             new_of_old, old_of_new, nvis = ops.visible_first(vis)
             plan["dec"] = dict(new_of_old=new_of_old, old_of_new=old_of_new)
             counts.append(nvis)
@@ -868,7 +875,8 @@ class SVGTransformer(nn.Module):
         else:
             cmd = commands.to(torch.float32).contiguous().view(N * G, S)
             arg = args.to(torch.float32).contiguous().view(N * G * S, -1)
-            key_mask, _vis, group_mask = ops.build_masks(cmd, S, G, EOS_ID, want_group_mask=two)
+            key_mask, _vis, group_mask = (ops.build_masks_lens if (two and S > 64) else ops.build_masks)(
+                cmd, S, G, EOS_ID, want_group_mask=two)
             self.last_packing = None
             groups = ops.group_index(cmd, S, M_ID) if enc.use_group else None
             src = Fn.EmbedFn.apply(rt, cmd.view(-1), arg, groups, N * G, S, PE_DROPOUT, 1,

@@ -481,17 +481,52 @@ def attention_tiles(seq_off, n_seq, max_rows=32):
     return tiles
 
 
+# the path-level stages of two-stage configs with paths of 65..256 tokens, bf16: the matrix-core kernels of
+# csrc/attention_long_mfma.hip (DSVG_LONG_MFMA=0: the VALU long kernels, padded or packed)
+LONG_MFMA = os.environ.get("DSVG_LONG_MFMA", "1") != "0"
+
+
+def _long_route(qkv, S, causal, seq_off, path_stage):
+    """S > 64: 'mfma' / 'packed' (VALU long kernels on the packed layout) / 'padded' (the padded VALU long kernels, rows
+    past n_seq * S zero-filled) / None (the one-stage route)"""
+    if S <= 64 or causal or not (path_stage or seq_off is not None):
+        return None
+    return "mfma" if (qkv.dtype == torch.bfloat16 and LONG_MFMA) else ("packed" if seq_off is not None else "padded")
+
+
 def attention_fwd(qkv, key_mask, n_seq, S, n_heads, scale, drop_p=0.0, drop_site=0, seed=None, seq_off=None,
-                  tiles=None, causal=False, only_row=None, out=None):
+                  tiles=None, causal=False, only_row=None, out=None, path_stage=False):
     """seq_off (int32 [n_seq+1], device): packed layout, sequence b = rows seq_off[b]..seq_off[b+1]-1 (<= S rows, all
     keys visible, key_mask must be None); rows past seq_off[n_seq] are zero-filled.
-    causal: query i attends keys j <= i (autoregressive decoder; dense layout only)."""
+    causal: query i attends keys j <= i (autoregressive decoder; dense layout only).
+    path_stage: a path-level stage of a two-stage config (S > 64, bf16: the matrix-core long kernels)."""
     _chk(qkv, key_mask, seed, seq_off)
     rows = qkv.shape[0]
     assert qkv.is_contiguous() and qkv.shape[1] == 3 * 32 * n_heads, "attention needs head_dim == 32"
     assert (rows >= n_seq * S) if seq_off is None else (key_mask is None and seq_off.numel() == n_seq + 1)
     if out is None:
         out = torch.empty((rows, 32 * n_heads), dtype=qkv.dtype, device=qkv.device)
+    route = _long_route(qkv, S, causal, seq_off, path_stage)
+    if route is not None:
+        assert key_mask is None or key_mask.dtype == torch.int32
+        sd = _p(seed) if drop_p > 0 else None
+        if route == "mfma":
+            _l.check(_l.load().dsvg_attention_long_mfma_fwd(qkv.data_ptr(), _p(key_mask), _p(seq_off), rows, out.data_ptr(),
+                                                            n_seq, S, n_heads, float(scale), float(drop_p), int(drop_site),
+                                                            sd, _stream()), "dsvg_attention_long_mfma_fwd")
+            if seq_off is None:
+                out[n_seq * S:].zero_()         # rows past the last sequence (a live prefix of the rows)
+        elif route == "padded":
+            _l.check(_l.load().dsvg_attention_long_fwd(_dt(qkv), qkv.data_ptr(), _p(key_mask), out.data_ptr(), n_seq, S,
+                                                       n_heads, float(scale), 0, -1, float(drop_p), int(drop_site), sd,
+                                                       _stream()), "dsvg_attention_long_fwd")
+            out[n_seq * S:].zero_()
+        else:
+            _l.check(_l.load().dsvg_attention_long_packed_fwd(_dt(qkv), qkv.data_ptr(), seq_off.data_ptr(), rows,
+                                                              out.data_ptr(), n_seq, S, n_heads, float(scale), float(drop_p),
+                                                              int(drop_site), sd, _stream()),
+                     "dsvg_attention_long_packed_fwd")
+        return out
     if S > 64:      # long sequences: key_mask holds valid-prefix lengths (build_masks)
         # only_row (with causal): the incremental decoding step - that query row alone is computed into `out`
         assert seq_off is None and rows == n_seq * S and (key_mask is None or key_mask.dtype == torch.int32)
@@ -515,11 +550,34 @@ def attention_fwd(qkv, key_mask, n_seq, S, n_heads, scale, drop_p=0.0, drop_site
 
 
 def attention_bwd(qkv, key_mask, dout, n_seq, S, n_heads, scale, drop_p=0.0, drop_site=0, seed=None, seq_off=None,
-                  tiles=None, causal=False):
+                  tiles=None, causal=False, path_stage=False):
     _chk(qkv, key_mask, dout, seed, seq_off)
     assert qkv.is_contiguous() and dout.is_contiguous() and dout.dtype == qkv.dtype
     assert seq_off is None or (key_mask is None and seq_off.numel() == n_seq + 1)
     dqkv = torch.empty_like(qkv)
+    route = _long_route(qkv, S, causal, seq_off, path_stage)
+    if route is not None:
+        assert key_mask is None or key_mask.dtype == torch.int32
+        assert seq_off is not None or qkv.shape[0] >= n_seq * S
+        sd = _p(seed) if drop_p > 0 else None
+        if route == "mfma":
+            _l.check(_l.load().dsvg_attention_long_mfma_bwd(qkv.data_ptr(), _p(key_mask), _p(seq_off), qkv.shape[0],
+                                                            dout.data_ptr(), dqkv.data_ptr(), n_seq, S, n_heads,
+                                                            float(scale), float(drop_p), int(drop_site), sd, _stream()),
+                     "dsvg_attention_long_mfma_bwd")
+            if seq_off is None:
+                dqkv[n_seq * S:].zero_()
+        elif route == "padded":
+            _l.check(_l.load().dsvg_attention_long_bwd(_dt(qkv), qkv.data_ptr(), _p(key_mask), dout.data_ptr(),
+                                                       dqkv.data_ptr(), n_seq, S, n_heads, float(scale), 0, float(drop_p),
+                                                       int(drop_site), sd, _stream()), "dsvg_attention_long_bwd")
+            dqkv[n_seq * S:].zero_()
+        else:
+            _l.check(_l.load().dsvg_attention_long_packed_bwd(_dt(qkv), qkv.data_ptr(), seq_off.data_ptr(), qkv.shape[0],
+                                                              dout.data_ptr(), dqkv.data_ptr(), n_seq, S, n_heads,
+                                                              float(scale), float(drop_p), int(drop_site), sd, _stream()),
+                     "dsvg_attention_long_packed_bwd")
+        return dqkv
     if S > 64:
         assert seq_off is None and qkv.shape[0] == n_seq * S and (key_mask is None or key_mask.dtype == torch.int32)
         _l.check(_l.load().dsvg_attention_long_bwd(_dt(qkv), qkv.data_ptr(), _p(key_mask), dout.data_ptr(),
@@ -647,6 +705,23 @@ def build_masks(commands, S, G=0, eos_id=4, want_group_mask=False):
     return key_mask, seq_visible, group_mask
 
 
+def build_masks_lens(commands, S, G=0, eos_id=4, want_group_mask=False):
+    """commands float32 [n_seq, S], S <= 256 -> lens int32 [n_seq] (first-EOS index, = seq_lens), seq_visible int32 [n_seq]
+    and, with want_group_mask, group_mask int64 [n_seq / G]: the masks of build_masks for two-stage configs with paths of
+    65..256 tokens"""
+    _chk(commands)
+    assert commands.dtype == torch.float32 and commands.is_contiguous()
+    n_seq = commands.numel() // S
+    dev = commands.device
+    lens = torch.empty(n_seq, dtype=torch.int32, device=dev)
+    seq_visible = torch.empty(n_seq, dtype=torch.int32, device=dev)
+    group_mask = torch.empty(n_seq // G, dtype=torch.int64, device=dev) if want_group_mask else None
+    _l.check(_l.load().dsvg_build_masks_lens(commands.data_ptr(), n_seq, S, G if want_group_mask else 1, eos_id,
+                                             lens.data_ptr(), seq_visible.data_ptr(), _p(group_mask), _stream()),
+             "dsvg_build_masks_lens")
+    return lens, seq_visible, group_mask
+
+
 def group_index(commands, S, m_id=0):
     _chk(commands)
     assert commands.dtype == torch.float32 and commands.is_contiguous()
@@ -724,6 +799,10 @@ def masked_mean_fwd(x, mask, n_seq, S, seq_off=None):
     assert x.is_contiguous() and (mask is not None or seq_off is not None)
     d = x.shape[1]
     out = torch.empty((n_seq, d), dtype=x.dtype, device=x.device)
+    if S > 64 and seq_off is not None:      # packed paths of 65..256 tokens
+        _l.check(_l.load().dsvg_packed_mean_fwd(_dt(x), x.data_ptr(), seq_off.data_ptr(), out.data_ptr(), n_seq, d,
+                                                _stream()), "dsvg_packed_mean_fwd")
+        return out
     if S > 64:      # long sequences: `mask` holds valid-prefix lengths (build_masks)
         assert seq_off is None and mask.dtype == torch.int32
         _l.check(_l.load().dsvg_prefix_mean_fwd(_dt(x), x.data_ptr(), mask.data_ptr(), out.data_ptr(), n_seq, S, d,
@@ -740,6 +819,10 @@ def masked_mean_bwd(dout, mask, n_seq, S, seq_off=None, total_rows=None):
     d = dout.shape[1]
     rows = n_seq * S if seq_off is None else int(total_rows)
     dx = torch.empty((rows, d), dtype=dout.dtype, device=dout.device)
+    if S > 64 and seq_off is not None:
+        _l.check(_l.load().dsvg_packed_mean_bwd(_dt(dout), dout.data_ptr(), seq_off.data_ptr(), rows, dx.data_ptr(), n_seq,
+                                                d, _stream()), "dsvg_packed_mean_bwd")
+        return dx
     if S > 64:
         assert seq_off is None and mask.dtype == torch.int32
         _l.check(_l.load().dsvg_prefix_mean_bwd(_dt(dout), dout.data_ptr(), mask.data_ptr(), dx.data_ptr(), n_seq, S, d,
@@ -795,6 +878,23 @@ def pack_tokens(commands, args, key_mask, n_seq, S):
     _l.check(_l.load().dsvg_pack_tokens(commands.data_ptr(), args.data_ptr(), key_mask.data_ptr(), n_seq, S, n_args,
                                         seq_off.data_ptr(), pcmd.data_ptr(), parg.data_ptr(), ppos.data_ptr(),
                                         _stream()), "dsvg_pack_tokens")
+    return seq_off, pcmd, parg, ppos
+
+
+def pack_tokens_lens(commands, args, lens, n_seq, S):
+    """pack_tokens driven by valid-prefix lengths (build_masks_lens), S <= 256"""
+    _chk(commands, args, lens)
+    assert commands.dtype == torch.float32 and args.dtype == torch.float32 and commands.is_contiguous() and \
+        args.is_contiguous() and commands.numel() == n_seq * S and lens.dtype == torch.int32 and lens.numel() == n_seq
+    n_args = args.numel() // (n_seq * S)
+    dev = commands.device
+    seq_off = torch.empty(n_seq + 1, dtype=torch.int32, device=dev)
+    pcmd = torch.empty(n_seq * S, dtype=torch.float32, device=dev)
+    parg = torch.empty((n_seq * S, n_args), dtype=torch.float32, device=dev)
+    ppos = torch.empty(n_seq * S, dtype=torch.int32, device=dev)
+    _l.check(_l.load().dsvg_pack_tokens_lens(commands.data_ptr(), args.data_ptr(), lens.data_ptr(), n_seq, S, n_args,
+                                             seq_off.data_ptr(), pcmd.data_ptr(), parg.data_ptr(), ppos.data_ptr(),
+                                             _stream()), "dsvg_pack_tokens_lens")
     return seq_off, pcmd, parg, ppos
 
 

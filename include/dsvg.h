@@ -39,8 +39,10 @@ extern "C" {
  *    out_proj.weight^T).
  * 8 (round 6): dsvg_gs_stack_fwd / dsvg_gs_stack_bwd added (one launch per STACK of group-stage layers).
  * 9 (round 6): dg_ld argument of dsvg_bcast_add_bwd / dsvg_bcast_add_bwd_masked (dg as a column block of a wider buffer).
- * 10: dsvg_ffn_gate_dw2 added (the gated dpre GEMM and the dW2 split-K GEMM of the fused FFN backward as one launch). */
-#define DSVG_ABI_VERSION 10
+ * 10: dsvg_ffn_gate_dw2 added (the gated dpre GEMM and the dW2 split-K GEMM of the fused FFN backward as one launch).
+ * 11: two-stage configs with paths of 65..256 tokens: dsvg_build_masks_lens, dsvg_pack_tokens_lens, dsvg_packed_mean_fwd /
+ *     bwd, dsvg_attention_long_packed_fwd / bwd, dsvg_attention_long_mfma_fwd / bwd added. */
+#define DSVG_ABI_VERSION 11
 
 const char* dsvg_last_error(void);
 int dsvg_version(void);
@@ -419,6 +421,44 @@ int dsvg_prefix_mean_fwd(int32_t dtype, const void* x, const int32_t* lens, void
                          void* stream);
 int dsvg_prefix_mean_bwd(int32_t dtype, const void* dout, const int32_t* lens, void* dx, int64_t n_seq, int32_t S,
                          int32_t d, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Two-stage configs with paths of 65..256 tokens (max_seq_len + 2 <= 256): the path-level stages (first encoder stage,
+ * second decoder stage) with lengths in place of the 64-bit masks.
+ *   build_masks_lens:   lens[b] = first-EOS index (= dsvg_seq_lens), seq_visible[b] = (number of EOS < S - 1), and the
+ *                       per-icon group bitmask (G <= 64), as dsvg_build_masks (deepsvg/model/model.py:128-131,
+ *                       deepsvg/model/utils.py:7-32)
+ *   pack_tokens_lens:   the packed layout of dsvg_pack_tokens driven by lens, S <= 256 (layers/functional.py:234-239,
+ *                       model/model.py:137)
+ *   packed_mean:        out[b,:] = mean of the packed rows seq_off[b] .. seq_off[b+1]-1 (model/model.py:137); the
+ *                       backward zero-fills rows [seq_off[n_seq], total_rows)
+ *   attention_long_packed:  the dsvg_attention_long_* VALU kernels on the packed layout (non-causal; rows past
+ *                       seq_off[n_seq] up to total_rows zero-filled), dropout rows (b H + h) S + i as in the padded layout
+ *                       (layers/functional.py:168,197-248)
+ *   attention_long_mfma:    bf16 matrix-core kernels of the same contract, padded (lens: keys j < lens[b], NULL = all)
+ *                       or packed (seq_off, lens NULL), head_dim 32, non-causal; same dropout element ids
+ * ------------------------------------------------------------------------------------------ */
+int dsvg_build_masks_lens(const float* commands, int64_t n_seq, int32_t S, int32_t G, int32_t eos_id, int32_t* lens,
+                          int32_t* seq_visible, uint64_t* group_mask, void* stream);
+int dsvg_pack_tokens_lens(const float* commands, const float* args, const int32_t* lens, int64_t n_seq, int32_t S,
+                          int32_t n_args, int32_t* seq_off, float* packed_commands, float* packed_args,
+                          int32_t* packed_pos, void* stream);
+int dsvg_packed_mean_fwd(int32_t dtype, const void* x, const int32_t* seq_off, void* out, int64_t n_seq, int32_t d,
+                         void* stream);
+int dsvg_packed_mean_bwd(int32_t dtype, const void* dout, const int32_t* seq_off, int64_t total_rows, void* dx,
+                         int64_t n_seq, int32_t d, void* stream);
+int dsvg_attention_long_packed_fwd(int32_t dtype, const void* qkv, const int32_t* seq_off, int64_t total_rows, void* out,
+                                   int64_t n_seq, int32_t S, int32_t n_heads, float scale, float drop_p,
+                                   uint32_t drop_site, const uint64_t* seed, void* stream);
+int dsvg_attention_long_packed_bwd(int32_t dtype, const void* qkv, const int32_t* seq_off, int64_t total_rows,
+                                   const void* dout, void* dqkv, int64_t n_seq, int32_t S, int32_t n_heads, float scale,
+                                   float drop_p, uint32_t drop_site, const uint64_t* seed, void* stream);
+int dsvg_attention_long_mfma_fwd(const void* qkv, const int32_t* lens, const int32_t* seq_off, int64_t total_rows,
+                                 void* out, int64_t n_seq, int32_t S, int32_t n_heads, float scale, float drop_p,
+                                 uint32_t drop_site, const uint64_t* seed, void* stream);
+int dsvg_attention_long_mfma_bwd(const void* qkv, const int32_t* lens, const int32_t* seq_off, int64_t total_rows,
+                                 const void* dout, void* dqkv, int64_t n_seq, int32_t S, int32_t n_heads, float scale,
+                                 float drop_p, uint32_t drop_site, const uint64_t* seed, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Hungarian self-matching (HierarchicalSelfMatching, deepsvg/model/config.py:101-108):
