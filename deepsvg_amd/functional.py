@@ -22,50 +22,28 @@ import torch
 
 from . import ops
 
-# fused FFN backward (hidden tile recomputed in the kernel) instead of the default: see LayerFn.backward
-FFN_BWD_FUSED = os.environ.get("DSVG_FFN_BWD_FUSED", "0") != "0"
 # the fused FFN kernels own 256 token rows per workgroup: below ~16k rows they cannot fill the 256 CUs and the three
 # unfused launches are faster (measured: 4096 rows 39-50 us fused vs 33 us unfused; 41k rows 56 vs 71 us)
 FFN_MIN_ROWS = int(os.environ.get("DSVG_FFN_MIN_ROWS", "16384"))
 # the fused attention block owns 8 tiles of <= 32 rows per workgroup (same granularity: unfused launches below this)
 ATTN_MIN_ROWS = int(os.environ.get("DSVG_ATTN_MIN_ROWS", "16384"))
-# fused-FFN backward: weight-gradient GEMMs right behind the producers of their operands (1) or at the end (0)
-FFN_BWD_ORDER = os.environ.get("DSVG_FFN_BWD_ORDER", "1") != "0"
-# dx and its dropout-masked copy from one ffn_bwd_dx launch instead of a drop_apply launch: measured SLOWER (8.52 vs 8.43
-# ms/step: the extra pass sits on the tail of a one-workgroup-per-CU kernel), so it is opt-in
-FFN_BWD_MASKED = int(os.environ.get("DSVG_FFN_BWD_MASKED", "0"))    # 1: every layer; 2: only layers without a conditioning row
-# (their bcast_add_bwd launch writes the masked copy anyway, BCAST_MASKED)
 # fused-FFN backward: dpre (the gated GEMM) and the linear2 weight gradient from one launch that stages dym / h once
 # (csrc/ffn_bwd_gate.hip; 0: the two launches)
 FFN_GATE_DW2 = os.environ.get("DSVG_FFN_GATE_DW2", "1") != "0"
 
-# the weight-gradient GEMMs of a layer of the 4096-row stages as one grouped launch (DSVG_GROUP_WGRAD=0: one by one)
-GROUP_WGRAD = os.environ.get("DSVG_GROUP_WGRAD", "1") != "0"
-# the decoder layers' bcast_add_bwd also writes the masked copy of dx1 the attention half needs (one read of dx1, no drop_apply launch)
-BCAST_MASKED = os.environ.get("DSVG_BCAST_MASKED", "1") != "0"
 # round 5: the LayerNorm backward that produces a layer's incoming gradient also writes that gradient with the residual-dropout
 # mask of the layer BELOW replayed on it (what that layer's FFN half reads): 9 drop_apply launches per step less
 LN_BWD_MASKED = os.environ.get("DSVG_LN_BWD_MASKED", "1") != "0"
 # round 5: the position / embedding tables' gradient reductions (add_pos_bwd, embed_scatter: 6 launches) join the deferred queue,
 # and the library queues segments of any width (csrc/gemm.hip: the heads' 7- and 2827-row gradients: 2 launches); 0 = as before
 DEFER_MORE = os.environ.get("DSVG_DEFER_MORE", "1") != "0"
-# round 5: ONE grouped weight-gradient launch per group-stage STACK (4 layers x 4 products) instead of one per layer
-STACK_GROUP = os.environ.get("DSVG_STACK_GROUP", "1") != "0"
-STACK_GROUP_SLICES = int(os.environ.get("DSVG_STACK_GROUP_SLICES", "8"))    # token slices per output tile of a product in that launch (8 =
-# the per-layer launches' partition: the bf16 slice sums, hence the gradients, are then the same numbers; 4 measured 0.1 % faster)
-# round 5: the group-stage backward kernel also emits the conditioning term's gradient (4 bcast_add_bwd launches + 4 dx1 stores less)
-GS_BWD_DG = os.environ.get("DSVG_GS_BWD_DG", "1") != "0"
 # round 5: the argument head's input-gradient product with its reduced dimension padded to the LDS-DMA GEMM's K step
 HEAD_KPAD = os.environ.get("DSVG_HEAD_KPAD", "1") != "0"
-# round 6: the layers of a decoder stack write the gradients of their conditioning rows side by side into ONE buffer (the column
-# blocks GlobalCondFn's concatenated products read): no concatenation launch; 0 = one tensor per layer + torch.cat
-COND_GRAD_SHARED = os.environ.get("DSVG_COND_GRAD_SHARED", "1") != "0"
 # round 6: the group-stage stacks as ONE launch per stack and direction (csrc/group_stage.hip gs_stack_*; 0: one launch per layer)
 GS_STACK = os.environ.get("DSVG_GS_STACK", "1") != "0"
-# attention backward of the large stages with the out_proj backward inside (no `dao = dx1m @ Wo` GEMM launch)
-ATTN_BWD_OUTPROJ = os.environ.get("DSVG_ATTN_BWD_OUTPROJ", "1") != "0"
-# ... which only exists on the MFMA attention kernels: the library's A/B knobs that route attention to the VALU kernels
-# (dsvg_attention_mfma_ok, csrc/attention_mfma.hip) must switch it off too instead of failing the backward pass
+# the attention backward with the out_proj backward inside (ops.attention_bwd_outproj) only exists on the MFMA attention kernels:
+# the library's A/B knobs that route attention to the VALU kernels (dsvg_attention_mfma_ok, csrc/attention_mfma.hip) must switch
+# it off too instead of failing the backward pass
 _ATTN_VALU = os.environ.get("DSVG_ATTN_VALU") is not None
 _ATTN_MFMA_MIN_S = int(os.environ.get("DSVG_ATTN_MFMA_MIN_S", "2"))
 # round 6: the attention half's input gradient (dqkv . W_in + LayerNorm backward + residual) as one launch, csrc/attn_bwd_dx.hip
@@ -103,13 +81,14 @@ class Runtime:
         # a two-stage model: its sequences of more than 64 tokens are paths (ops.attention_fwd / bwd path_stage)
         self.path_stage = False
         # base address of a stack's projected conditioning rows (GlobalCondFn's [n_seq, n * 256] product) -> the buffer its layers'
-        # backward passes write their gradients into, side by side (COND_GRAD_SHARED)
+        # backward passes write their gradients into, side by side (the column blocks GlobalCondFn's concatenated products
+        # read: no concatenation launch)
         self.cond_grad = {}
 
     def cond_grad_block(self, z, rows):
         """z: the conditioning rows a layer received.  If they are column block i of a row-major [*, n * w] product (GlobalCondFn),
         -> column block i of the stack's shared [rows, n * w] gradient buffer (created by the first layer that asks), else None"""
-        if not COND_GRAD_SHARED or z is None or z.dim() != 2 or z.stride(1) != 1 or z.dtype != torch.bfloat16:
+        if z is None or z.dim() != 2 or z.stride(1) != 1 or z.dtype != torch.bfloat16:
             return None
         w, ld = z.shape[1], z.stride(0)
         if ld <= w or ld % w or w % 8 or w > 512:
@@ -149,7 +128,7 @@ class Runtime:
 
     def grouping(self):
         """context manager around a run of independent weight-gradient GEMMs: one launch for all of them (ops.GROUP)"""
-        return ops.GROUP if GROUP_WGRAD else _NULL_CTX
+        return ops.GROUP
 
     def p(self, rate):
         """effective dropout probability"""
@@ -190,23 +169,29 @@ def _wgrad(rt, param, dy, x, *, a_drop_p=0.0, a_drop_site=0):
     return out
 
 
-def _wbgrad(rt, weight, bias, dy, x, blocks=None):
+def _wbgrad(rt, weight, bias, dy, x, blocks=None, *, out=None, split=None, defer=True):
     """(dW, db) of y = x W^T + b from dy: db[n] = sum_t dy[t, n] is the row sum of the GEMM's A operand, so it
     rides on the weight-gradient GEMM (an extra MFMA against ones in a few workgroups) whenever that GEMM is
     split over tokens; otherwise a separate column-sum launch.  blocks: target workgroup count of this GEMM (default: a
-    launch of its own, one workgroup per CU; members of a grouped launch share the chip)."""
-    n_out, k_in = weight.shape
-    split = ops.split_k_for(n_out, k_in, dy.shape[0], target_blocks=blocks)
-    dw = rt.grad_out(weight)
-    db = rt.grad_out(bias)
-
-    with rt.deferring(), _wgrad_tag():
+    launch of its own, one workgroup per CU; members of a grouped launch share the chip).
+    out = (dW, db) and split: the caller's own output tensors (a row range, several parameters at once, a packed layout) and
+    the split factor it chose for them, instead of the gradient slots of weight / bias; defer=False: results read at once."""
+    if split is None:
+        split = ops.split_k_for(*weight.shape, dy.shape[0], target_blocks=blocks)
+    dw, db = out if out is not None else (rt.grad_out(weight), rt.grad_out(bias))
+    with (rt.deferring() if defer else _NULL_CTX), _wgrad_tag():
         if split > 1:
-            ops.gemm(dy, x, a_kc=False, b_kc=False, out=dw.view(n_out, k_in), split_k=split, rowsum=db)
+            ops.gemm(dy, x, a_kc=False, b_kc=False, out=dw, split_k=split, rowsum=db)
         else:
-            ops.gemm(dy, x, a_kc=False, b_kc=False, out=dw.view(n_out, k_in))
+            ops.gemm(dy, x, a_kc=False, b_kc=False, out=dw)
             ops.colsum(dy, out=db)
     return dw, db
+
+
+def _group_blocks(w):
+    """target workgroup count of w's weight-gradient GEMM as a member of a grouped launch: 8 token slices per 128 x 128 output
+    tile (a layer's four products have 32 - 36 tiles between them: together they fill the chip once)"""
+    return 8 * -(-w.shape[0] // 128) * -(-w.shape[1] // 128)
 
 
 def _bgrad(rt, param, dy, *, drop_p=0.0, drop_site=0):
@@ -355,8 +340,7 @@ class LatentChainFn(torch.autograd.Function):
         with rt.grouping():
             for i in range(n + 1):
                 w, b = wb[2 * i], wb[2 * i + 1]
-                blocks = (8 * -(-w.shape[0] // 128) * -(-w.shape[1] // 128)) if GROUP_WGRAD else None
-                grads += list(_wbgrad(rt, w, b, dpre[i] if i < n else dout, zin[i], blocks))
+                grads += list(_wbgrad(rt, w, b, dpre[i] if i < n else dout, zin[i], _group_blocks(w)))
         return (None, dz0, *grads)
 
 
@@ -683,13 +667,7 @@ class GlobalCondFn(torch.autograd.Function):
                 else:       # (not reached by any shipped config: one product into a temporary, then n copies)
                     dwc = torch.empty((n_out, k_in), dtype=torch.float32, device=z.device)
                     dbc = torch.empty(n_out, dtype=torch.float32, device=z.device)
-                split = ops.split_k_for(n_out, k_in, z.shape[0])
-                with (rt.deferring() if adj else _NULL_CTX), _wgrad_tag():
-                    if split > 1:
-                        ops.gemm(dgcat, z, a_kc=False, b_kc=False, out=dwc, split_k=split, rowsum=dbc)
-                    else:
-                        ops.gemm(dgcat, z, a_kc=False, b_kc=False, out=dwc)
-                        ops.colsum(dgcat, out=dbc)
+                _wbgrad(rt, None, None, dgcat, z, out=(dwc, dbc), split=ops.split_k_for(n_out, k_in, z.shape[0]), defer=adj)
                 if not adj:
                     r0 = 0
                     for (w, _b), dw, db in zip(pairs, dws, dbs):
@@ -702,8 +680,7 @@ class GlobalCondFn(torch.autograd.Function):
         else:
             with (rt.grouping() if small else _NULL_CTX):
                 for (w, b), dg in zip(pairs, dg_blocks()):
-                    blocks = (8 * -(-w.shape[0] // 128) * -(-w.shape[1] // 128)) if (small and GROUP_WGRAD) else None
-                    grads += list(_wbgrad(rt, w, b, dg, z, blocks))
+                    grads += list(_wbgrad(rt, w, b, dg, z, _group_blocks(w) if small else None))
         dz = None
         if ctx.needs_input_grad[1]:
             if cat_ok:
@@ -730,6 +707,45 @@ class GlobalCondFn(torch.autograd.Function):
         return (None, dz, *grads)
 
 
+def _gs_eligible(rt, x, key_mask, n_seq, S, n_heads):
+    """the shapes the group-stage kernels (csrc/group_stage.hip: a whole block, or a whole stack, per launch) are built for:
+    dense short sequences, fewer rows than the fused kernels of the large stages need to fill the chip"""
+    return (rt.store is not None and x.dtype == torch.bfloat16 and n_heads == 8 and x.shape[1] == 256 and 32 % S == 0
+            and x.shape[0] == n_seq * S and x.shape[0] < min(ATTN_MIN_ROWS, FFN_MIN_ROWS)
+            and (key_mask is None or key_mask.dtype == torch.int64))
+
+
+def _attn_fused_eligible(rt, x, rows, key_mask, n_heads, causal):
+    """what the fused attention kernels of the large stages (csrc/attn_fused.hip forward, ops.attention_bwd_outproj backward)
+    have in common; rows: the rows THIS launch would run on (the backward pass may run on a live prefix only)"""
+    return (rt.store is not None and x.dtype == torch.bfloat16 and n_heads == 8 and x.shape[1] == 256 and not causal
+            and rows >= ATTN_MIN_ROWS and (key_mask is None or key_mask.dtype == torch.int64))
+
+
+def _gs_queue_wgrads(rt, close, ffn2, ffn1, out_proj, in_proj, cond=None):
+    """queue the weight-gradient products of one group-stage layer, each given as (weight, bias, dy, x) - independent of each
+    other, 64-256 workgroups each: one grouped launch per layer, or under a trainer (rt.defer: the results are only read
+    after its flush) ONE for all the layers of the stack, 16 products for 4 layers = the launch's table size, which `close`
+    (the stack's first layer, the last one of the backward pass) launches; the list keeps the operands alive until then.
+    cond = the conditioning row's (wg, bg, dg, z): a product only where the layer projects the row itself (wg).
+    8 token slices per tile in both cases, so the bf16 slice sums, hence the gradients, are the same numbers (4 measured 0.1 %
+    faster, profiles/r05_ab_stack_group_slices.log).  -> the (dW, db) pairs in the order of the arguments"""
+    def queue(pr):
+        return _wbgrad(rt, *pr, _group_blocks(pr[0]))
+    keep = rt.stack_group_begin() if rt.defer else None
+    with (rt.grouping() if keep is None else _NULL_CTX):
+        with ops.tag("ffn"):
+            g2, g1 = queue(ffn2), queue(ffn1)
+        gc = queue(cond) if (cond is not None and cond[0] is not None) else (None, None)
+        go, gi = queue(out_proj), queue(in_proj)
+    if keep is not None:
+        for pr in (ffn2, ffn1, out_proj, in_proj, cond or ()):
+            keep += pr[2:]
+        if close:
+            rt.stack_group_end()
+    return g2, g1, go, gi, gc
+
+
 class LayerFn(torch.autograd.Function):
     """One pre-LN transformer block.  With z: the 'global' decoder block (x += linear_global(z) broadcast over
     the sequence); with l: the label-conditioned variant (x += linear_global2(l)).
@@ -753,10 +769,7 @@ class LayerFn(torch.autograd.Function):
         want_bwd = any(ctx.needs_input_grad)         # (grad mode itself is off inside Function.forward)
         ctx.gs = False
         gs = None
-        if (rt.store is not None and x.dtype == torch.bfloat16 and not causal and seq_off is None and l is None
-                and n_heads == 8 and d == 256 and 32 % S == 0 and x.shape[0] == n_seq * S
-                and x.shape[0] < min(ATTN_MIN_ROWS, FFN_MIN_ROWS) and live is None
-                and (key_mask is None or key_mask.dtype == torch.int64)):
+        if _gs_eligible(rt, x, key_mask, n_seq, S, n_heads) and not causal and seq_off is None and l is None and live is None:
             gs = rt.store.gs(win)
         if gs is not None:
             # the short-sequence ("group") stages: the whole block in ONE launch (csrc/group_stage.hip); with a backward pass
@@ -779,9 +792,8 @@ class LayerFn(torch.autograd.Function):
             return x2
         att = None
         # (p <= 0.5: the fused kernel's packed 16-bit dropout code, csrc/attn_fused.hip; a higher rate takes the unfused launches)
-        if (rt.store is not None and x.dtype == torch.bfloat16 and x.shape[0] >= ATTN_MIN_ROWS and S <= 32 and not causal
-                and n_heads == 8 and d == 256 and (seq_off is None or tiles is not None) and p <= 0.5
-                and (key_mask is None or key_mask.dtype == torch.int64)):
+        if (_attn_fused_eligible(rt, x, x.shape[0], key_mask, n_heads, causal) and S <= 32
+                and (seq_off is None or tiles is not None) and p <= 0.5):
             att = rt.store.attn(win)
         z_fused = False
         split = 0
@@ -862,7 +874,7 @@ class LayerFn(torch.autograd.Function):
             # normalised rows xh; the inference call stores nothing but the result.
             mean2 = rstd2 = None
             with ops.tag("ffn"):
-                if want_bwd and not FFN_BWD_FUSED:
+                if want_bwd:
                     x2, h, xn2, _rstd = ops.ffn_fwd(x1, ffn[0], ffn[2], b2.detach(), 1e-5, p, site0 + 3, site0 + 4, rt.seed,
                                                     train=True)
                 else:
@@ -901,39 +913,23 @@ class LayerFn(torch.autograd.Function):
             # one launch for the whole input-gradient chain of the block (csrc/group_stage.hip); it hands over the token-major
             # operands of the four weight-gradient GEMMs and the LayerNorm parameter gradients
             gs = rt.store.gs(win)
-            fuse_dg = GS_BWD_DG and z is not None      # the conditioning term's gradient from the same launch (no dx1 round trip)
+            # (with the conditioning term's gradient from the same launch: no dx1 round trip + bcast_add_bwd launch,
+            # profiles/r05_ab_gs_bwd_dg.log)
             with rt.deferring(), ops.tag("gs"):
                 (dx, dx1, dym, dpre, dx1m, dqkv, dn2w, dn2b, dn1w, dn1b, *dg_) = ops.gs_layer_bwd(
                     dx2, gs[1], x, mean1, rstd1, qkv, x1, mean2, rstd2, h, n1w.detach(), n2w.detach(), key_mask, n_seq, S,
-                    ctx.scale, p, s0, rt.seed, want_dx1=z is not None and not fuse_dg, dgamma2=rt.grad_out(n2w),
-                    dbeta2=rt.grad_out(n2b), dgamma1=rt.grad_out(n1w), dbeta1=rt.grad_out(n1b), want_dg=fuse_dg)
-            dz = dwg = dbg = dg = None
+                    ctx.scale, p, s0, rt.seed, want_dx1=False, dgamma2=rt.grad_out(n2w),
+                    dbeta2=rt.grad_out(n2b), dgamma1=rt.grad_out(n1w), dbeta1=rt.grad_out(n1b), want_dg=z is not None)
+            dz = dg = None
             if z is not None:
-                dg = dg_[0] if fuse_dg else ops.bcast_add_bwd(dx1, n_seq, S, p, s0 + 2, rt.seed)
+                dg = dg_[0]
                 if wg is None:
                     dz = dg                 # `z` was the projected row itself: its gradient goes to GlobalCondFn
                 elif ctx.needs_input_grad[3]:
                     dz = ops.gemm(dg, rt.w(wg), b_kc=False)
-            # the layer's weight-gradient GEMMs: independent of each other, 64-256 workgroups each - one grouped launch
-            # (32 - 36 output tiles of 128 x 128 between them: 8 token slices each fill the chip once, together)
-            nsl = STACK_GROUP_SLICES if (STACK_GROUP and GROUP_WGRAD and rt.defer) else 8
-            gb = (lambda w_: nsl * -(-w_.shape[0] // 128) * -(-w_.shape[1] // 128)) if GROUP_WGRAD else (lambda w_: None)
-            # STACK_GROUP (round 5): the products of ALL the stack's layers wait for one launch (16 of them for 4 layers: the
-            # launch's table size) instead of one launch per layer.  Their results are only read after the trainer's flush
-            # (rt.defer), their operands are kept alive by the list until the launch
-            keep = rt.stack_group_begin() if (STACK_GROUP and GROUP_WGRAD and rt.defer) else None
-            with (rt.grouping() if keep is None else _NULL_CTX):
-                with ops.tag("ffn"):
-                    dw2, db2 = _wbgrad(rt, w2, b2, dym, h, gb(w2))
-                    dw1, db1 = _wbgrad(rt, w1, b1, dpre, xn2, gb(w1))
-                if z is not None and wg is not None:
-                    dwg, dbg = _wbgrad(rt, wg, bg, dg, z, gb(wg))
-                dwo, dbo = _wbgrad(rt, wo, bo, dx1m, ao, gb(wo))
-                dwin, dbin = _wbgrad(rt, win, bin_, dqkv, xn1, gb(win))
-            if keep is not None:
-                keep += [dym, h, dpre, xn2, dx1m, ao, dqkv, xn1, dg, z]
-                if ctx.first_in_stack:
-                    rt.stack_group_end()
+            (dw2, db2), (dw1, db1), (dwo, dbo), (dwin, dbin), (dwg, dbg) = _gs_queue_wgrads(
+                rt, ctx.first_in_stack, (w2, b2, dym, h), (w1, b1, dpre, xn2), (wo, bo, dx1m, ao), (win, bin_, dqkv, xn1),
+                cond=(wg if z is not None else None, bg, dg, z))
             return (None, dx, None, dz, None, None, None, None, None, None,
                     dn1w, dn1b, dwin, dbin, dwo, dbo, dn2w, dn2b, dw1, db1, dw2, db2, dwg, dbg, None, None, None, None, None,
                     None, None, None)
@@ -941,7 +937,7 @@ class LayerFn(torch.autograd.Function):
         # end of its backward pass - slower, each product right behind the launch that wrote its operand hits the memory-side
         # cache - and the same GEMMs queued onto a second stream beside the group stages - slower inside the step's hipGraph)
         if ctx.ffn_fused:
-            pb, b1f, w2p = rt.store.ffn(w1)[1:]
+            pb, _b1f, w2p = rt.store.ffn(w1)[1:]
             T = x1.shape[0]
             with ops.tag("ffn"):
                 g2p = torch.empty((256, 512), dtype=torch.float32, device=x1.device)
@@ -949,61 +945,32 @@ class LayerFn(torch.autograd.Function):
                 db1p = torch.empty(512, dtype=torch.float32, device=x1.device)
                 db2 = rt.grad_out(b2)
                 s2, s1 = ops.split_k_for(256, 512, T), ops.split_k_for(512, 256, T)
-
-                def wgrad2(dym, hp):        # G2p = dym^T h (fragment-ordered columns), db2 = its row sums
+                # The forward kernel stored h (fragment-ordered columns) and xh.  dym = residual mask replayed once;
+                # dpre = (dym . W2p) gated by h (h > 0 <=> ReLU passed AND kept) in one GEMM; dx by the fused kernel
+                # (dpre . W1' with the LayerNorm backward in its epilogue).  Each weight-gradient GEMM runs right
+                # behind the launch that produced its token-major operand (dym, dpre: 65 / 130 MB that are then still
+                # partly in the memory-side cache), not at the end
+                # (measured slower: the fully fused ops.ffn_bwd, which recomputes the hidden tile but writes h, dpre, xh AND dym,
+                # profiles/r02_ffn_microbench.log)
+                # (round 4, MI355X: the three launches below as ONE kernel - dsvg_ffn_bwd_one, the mirror image of ffn_fwd -
+                # were bit-identical and 13 % faster in isolation (93 -> 80 us at 63 k rows) but 0.4 % SLOWER inside the
+                # step, where dym already comes from the masked bcast_add_bwd and dpre is read back from the memory-side
+                # cache; removed.  profiles/r04_experimental_ffn_bwd_one.log, r04_experimental_ab.log)
+                hp, xh = h, xn2
+                dym = dx2_masked if dx2_masked is not None else ops.drop_apply(dx2, p, s0 + 4, rt.seed)
+                if (FFN_GATE_DW2 and s2 > 1 and dym.is_cuda and dym.dtype == torch.bfloat16
+                        and dym.is_contiguous() and hp.is_contiguous() and w2p.is_contiguous()):
+                    # both products of the (dym, h) tiles from one staging: dpre bit-identical, G2p / db2 queued as
+                    # the weight-gradient GEMM's split-K slices would be
                     with rt.deferring():
-                        if s2 > 1:
-                            ops.gemm(dym, hp, a_kc=False, b_kc=False, out=g2p, split_k=s2, rowsum=db2)
-                        else:
-                            ops.gemm(dym, hp, a_kc=False, b_kc=False, out=g2p)
-                            ops.colsum(dym, out=db2)
-
-                def wgrad1(dpre, xh):       # G1p = dpre^T xh, db1' = its row sums
-                    with rt.deferring():
-                        if s1 > 1:
-                            ops.gemm(dpre, xh, a_kc=False, b_kc=False, out=g1p, split_k=s1, rowsum=db1p)
-                        else:
-                            ops.gemm(dpre, xh, a_kc=False, b_kc=False, out=g1p)
-                            ops.colsum(dpre, out=db1p)
-
-                if h is None:
-                    # fully fused variant (opt-in, DSVG_FFN_BWD_FUSED=1): hidden tile recomputed from x1, both dropout
-                    # masks replayed in the kernel; measured slower than the default below (it writes h, dpre, xh AND dym)
-                    dx1, hp, dpre, xh, dym = ops.ffn_bwd(x1, dx2, pb, b1f, 1e-5, p, s0 + 3, s0 + 4, rt.seed)
-                    wgrad2(dym, hp)
-                    wgrad1(dpre, xh)
+                        dpre = ops.ffn_gate_dw2(dym, hp, w2p, inv_keep, g2p, db2, s2)
                 else:
-                    # default: the forward kernel stored h (fragment order) and xh.  dym = residual mask replayed once;
-                    # dpre = (dym . W2p) gated by h (h > 0 <=> ReLU passed AND kept) in one GEMM; dx by the fused kernel
-                    # (dpre . W1' with the LayerNorm backward in its epilogue).  Each weight-gradient GEMM runs right
-                    # behind the launch that produced its token-major operand (dym, dpre: 65 / 130 MB that are then still
-                    # partly in the memory-side cache) instead of at the end
-                    hp, xh = h, xn2
-                    # (round 4, MI355X: the three launches below as ONE kernel - dsvg_ffn_bwd_one, the mirror image of ffn_fwd -
-                    # were bit-identical and 13 % faster in isolation (93 -> 80 us at 63 k rows) but 0.4 % SLOWER inside the
-                    # step, where dym already comes from the masked bcast_add_bwd and dpre is read back from the memory-side
-                    # cache; removed.  profiles/r04_experimental_ffn_bwd_one.log, r04_experimental_ab.log)
-                    dym = dx2_masked if dx2_masked is not None else ops.drop_apply(dx2, p, s0 + 4, rt.seed)
-                    if (FFN_GATE_DW2 and FFN_BWD_ORDER and s2 > 1 and dym.is_cuda and dym.dtype == torch.bfloat16
-                            and dym.is_contiguous() and hp.is_contiguous() and w2p.is_contiguous()):
-                        # both products of the (dym, h) tiles from one staging: dpre bit-identical, G2p / db2 queued as
-                        # wgrad2's split-K slices would be
-                        with rt.deferring():
-                            dpre = ops.ffn_gate_dw2(dym, hp, w2p, inv_keep, g2p, db2, s2)
-                    else:
-                        if FFN_BWD_ORDER:
-                            wgrad2(dym, hp)
-                        dpre = ops.gemm(dym, w2p, b_kc=False, gate=hp, gate_scale=inv_keep)
-                    if FFN_BWD_ORDER:
-                        wgrad1(dpre, xh)
-                    # (the same launch also hands over dx1 with the attention residual's dropout mask replayed on it)
-                    if FFN_BWD_MASKED == 1 or (FFN_BWD_MASKED == 2 and z is None and p > 0):
-                        dx1, dx1m = ops.ffn_bwd_dx(dpre, x1, dx2, pb, masked=(p, s0 + 1, rt.seed))
-                    else:
-                        dx1 = ops.ffn_bwd_dx(dpre, x1, dx2, pb)
-                    if not FFN_BWD_ORDER:
-                        wgrad2(dym, hp)
-                        wgrad1(dpre, xh)
+                    _wbgrad(rt, None, None, dym, hp, out=(g2p, db2), split=s2)     # G2p = dym^T h, db2 = its row sums
+                    dpre = ops.gemm(dym, w2p, b_kc=False, gate=hp, gate_scale=inv_keep)
+                _wbgrad(rt, None, None, dpre, xh, out=(g1p, db1p), split=s1)        # G1p = dpre^T xh, db1' = its row sums
+                # (measured slower, +1.5 %: this launch also writing dx1 with the attention residual's dropout mask replayed on
+                # it, `masked=`, instead of the drop_apply / bcast_add_bwd below - profiles/r05_ab_ffn_bwd_masked_rejected.log)
+                dx1 = ops.ffn_bwd_dx(dpre, x1, dx2, pb)
                 dw1, db1, dw2 = rt.grad_out(w1), rt.grad_out(b1), rt.grad_out(w2)
                 dn2w, dn2b = rt.grad_out(n2w), rt.grad_out(n2b)
                 # (aliases of the gradient tensors: AccumulateGrad adopts a returned gradient only while nobody else
@@ -1041,7 +1008,7 @@ class LayerFn(torch.autograd.Function):
             vec = dx1.dtype == torch.bfloat16 and dx1.is_contiguous() and dx1.shape[1] % 8 == 0 and dx1.shape[1] <= 512
             # (hoisted conditioning rows: the gradient goes straight into this layer's column block of the stack's shared buffer)
             dg_out = rt.cond_grad_block(z, n_seq_full) if (wg is None and vec and dx1.data_ptr() % 16 == 0) else None
-            if BCAST_MASKED and dx1m is None and p > 0 and vec and n_seq * S <= dx1.shape[0] <= n_seq_full * S:
+            if p > 0 and vec and n_seq * S <= dx1.shape[0] <= n_seq_full * S:
                 dg, dx1m = ops.bcast_add_bwd(dx1, n_seq, S, p, s0 + 2, rt.seed, n_seq_out=n_seq_full, mask_site=s0 + 1, out=dg_out)
             else:
                 dg = ops.bcast_add_bwd(dx1, n_seq, S, p, s0 + 2, rt.seed, n_seq_out=n_seq_full, out=dg_out)
@@ -1056,9 +1023,8 @@ class LayerFn(torch.autograd.Function):
             dx1m = ops.drop_apply(dx1, p, s0 + 1, rt.seed)
         dwo, dbo = _wbgrad(rt, wo, bo, dx1m, ao)
         wob = None
-        if (ATTN_BWD_OUTPROJ and not _ATTN_VALU and S >= _ATTN_MFMA_MIN_S
-                and rt.store is not None and x.dtype == torch.bfloat16 and H == 8 and x.shape[1] == 256
-                and not ctx.causal and x.shape[0] >= ATTN_MIN_ROWS and (key_mask is None or key_mask.dtype == torch.int64)
+        # (x: the live row prefix, if one is armed - a prefix below ATTN_MIN_ROWS takes the unfused arm)
+        if (not _ATTN_VALU and S >= _ATTN_MFMA_MIN_S and _attn_fused_eligible(rt, x, x.shape[0], key_mask, H, ctx.causal)
                 and ((seq_off is None and 16 < S <= 32 and x.shape[0] >= n_seq * S) or (seq_off is not None and ctx.tiles is not None))):
             wob = rt.store.attn_bwd(win)
         if wob is not None:
@@ -1107,10 +1073,8 @@ class LayerFn(torch.autograd.Function):
 # --------------------------------------------------------------------------------------------------
 def gs_stack_eligible(rt, x, key_mask, n_seq, S, n_heads, n_layers, wins):
     """the conditions of LayerFn's one-launch-per-layer route (csrc/group_stage.hip), for every layer of the stack"""
-    return (GS_STACK and rt.store is not None and x.dtype == torch.bfloat16 and n_heads == 8 and x.dim() == 2 and x.shape[1] == 256
-            and 32 % S == 0 and x.shape[0] == n_seq * S and x.shape[0] < min(ATTN_MIN_ROWS, FFN_MIN_ROWS)
-            and 1 <= n_layers <= ops.GS_STACK_MAX and (key_mask is None or key_mask.dtype == torch.int64)
-            and all(rt.store.gs(w) is not None for w in wins))
+    return (GS_STACK and x.dim() == 2 and _gs_eligible(rt, x, key_mask, n_seq, S, n_heads)
+            and 1 <= n_layers <= ops.GS_STACK_MAX and all(rt.store.gs(w) is not None for w in wins))
 
 
 class GsStackFn(torch.autograd.Function):
@@ -1167,27 +1131,14 @@ class GsStackFn(torch.autograd.Function):
                                dbeta1=rt.grad_out(n1b)))
         with rt.deferring(), ops.tag("gs"):
             dx, ops_, dgcat = ops.gs_stack_bwd(dx2.contiguous(), layers, key_mask, n_seq, S, ctx.scale, p, rt.seed, want_dg=has_g)
-        # the weight-gradient products, queued exactly as LayerFn.backward queues them layer by layer (last layer first): ONE grouped
-        # launch for the stack (STACK_GROUP) or one per layer
-        stack = STACK_GROUP and GROUP_WGRAD and rt.defer
-        nsl = STACK_GROUP_SLICES if stack else 8
-        gb = (lambda w_: nsl * -(-w_.shape[0] // 128) * -(-w_.shape[1] // 128)) if GROUP_WGRAD else (lambda w_: None)
+        # the weight-gradient products, queued as LayerFn.backward queues them layer by layer (last layer first)
         grads = [None] * (per * n)
         for i in range(n - 1, -1, -1):
             x2, mean1, rstd1, xn1, qkv, ao, x1, mean2, rstd2, xn2, h = acts[i]
             n1w, n1b, win, bin_, wo, bo, n2w, n2b, w1, b1, w2, b2 = prm[i]
             dym, dpre, dx1m, dqkv = ops_[i]
-            keep = rt.stack_group_begin() if stack else None
-            with (rt.grouping() if keep is None else _NULL_CTX):
-                with ops.tag("ffn"):
-                    dw2, db2 = _wbgrad(rt, w2, b2, dym, h, gb(w2))
-                    dw1, db1 = _wbgrad(rt, w1, b1, dpre, xn2, gb(w1))
-                dwo, dbo = _wbgrad(rt, wo, bo, dx1m, ao, gb(wo))
-                dwin, dbin = _wbgrad(rt, win, bin_, dqkv, xn1, gb(win))
-            if keep is not None:
-                keep += [dym, h, dpre, xn2, dx1m, ao, dqkv, xn1]
-                if i == 0:
-                    rt.stack_group_end()
+            (dw2, db2), (dw1, db1), (dwo, dbo), (dwin, dbin), _ = _gs_queue_wgrads(
+                rt, i == 0, (w2, b2, dym, h), (w1, b1, dpre, xn2), (wo, bo, dx1m, ao), (win, bin_, dqkv, xn1))
             L = layers[i]
             grads[per * i:per * i + 12] = [L["dgamma1"], L["dbeta1"], dwin, dbin, dwo, dbo, L["dgamma2"], L["dbeta2"], dw1, db1, dw2, db2]
             if has_g:
@@ -1369,11 +1320,7 @@ class ArgsHeadLossFn(torch.autograd.Function):
             with rt.deferring(), _wgrad_tag():
                 for t in (dw[:r0], dw[r1:], db[:r0], db[r1:]):       # (inside the scope: the fills ride on the flush)
                     ops.zero_(t) if DEFER_MORE else t.zero_()
-                if split > 1:
-                    ops.gemm(dl, xc, a_kc=False, b_kc=False, out=dw[r0:r1], split_k=split, rowsum=db[r0:r1])
-                else:
-                    ops.gemm(dl, xc, a_kc=False, b_kc=False, out=dw[r0:r1])
-                    ops.colsum(dl, out=db[r0:r1])
+                _wbgrad(rt, None, None, dl, xc, out=(dw[r0:r1], db[r0:r1]), split=split)
             if w_ext is not None:       # (dl's buffer over its whole padded width)
                 dxc = ops.gemm(torch.as_strided(dl, (dl.shape[0], w_ext.shape[0]), (dl.stride(0), 1)), w_ext, b_kc=False)
             else:

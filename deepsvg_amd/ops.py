@@ -209,7 +209,7 @@ class _GroupScope:
     they are locals of the code inside the block."""
     active = None       # profiling only: {tag: [flops, bytes]} of the members queued in the open scope
     depth = {}          # stream key -> nesting depth: only the outermost block opens / closes the library's scope (a block
-                        # inside a stack-level scope - functional.STACK_GROUP - must not launch the stack's queue early)
+                        # inside a stack-level scope - functional.Runtime.stack_group_begin - must not launch the stack's queue early)
 
     def __enter__(self):
         self._key = key = _stream_key()

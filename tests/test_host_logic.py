@@ -822,7 +822,7 @@ def test_trainer_gradless_slots_follow_call_shapes_and_reflattening(emulated_ops
 
 def test_group_scope_nests():
     """ops.GROUP (one grouped weight-gradient launch per block): a block inside an open block - a per-layer scope inside the
-    stack-level scope of functional.STACK_GROUP - must not close the outer one; only the outermost exit launches"""
+    stack-level scope of a group-stage stack (Runtime.stack_group_begin) - must not close the outer one; only the outermost exit launches"""
     from deepsvg_amd import ops
     key = ops._stream_key()
     assert ops._GroupScope.depth.get(key, 0) == 0
