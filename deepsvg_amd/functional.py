@@ -969,7 +969,10 @@ class LayerFn(torch.autograd.Function):
                     dpre = ops.gemm(dym, w2p, b_kc=False, gate=hp, gate_scale=inv_keep)
                 _wbgrad(rt, None, None, dpre, xh, out=(g1p, db1p), split=s1)        # G1p = dpre^T xh, db1' = its row sums
                 # (measured slower, +1.5 %: this launch also writing dx1 with the attention residual's dropout mask replayed on
-                # it, `masked=`, instead of the drop_apply / bcast_add_bwd below - profiles/r05_ab_ffn_bwd_masked_rejected.log)
+                # it, `masked=`, instead of the drop_apply / bcast_add_bwd below - profiles/r05_ab_ffn_bwd_masked_rejected.log.
+                # The mode stays compiled in: with the masked tail taken out of ffn_bwd_dx_kernel - three ways tried - hipcc
+                # gives the instantiation this call runs 20-28 bytes of scratch and 6 scratch instructions in its epilogue,
+                # against 0 with it)
                 dx1 = ops.ffn_bwd_dx(dpre, x1, dx2, pb)
                 dw1, db1, dw2 = rt.grad_out(w1), rt.grad_out(b1), rt.grad_out(w2)
                 dn2w, dn2b = rt.grad_out(n2w), rt.grad_out(n2b)

@@ -1306,7 +1306,7 @@ def ffn_fwd(x, packed_fwd_layer, b1f, b2, eps=1e-5, drop_p=0.0, site_hidden=0, s
     stages: None = the library's choice (half-size workgroups up to 32,768 rows, packed activation code), 2 = half-size
     workgroups, 3 / 4 = the 256-row workgroups with that many weight-ring slots, all three with the scalar activation code and
     bit-identical; 7 / 6 = half-size / 256-row workgroups with the packed activation code (bit-identical to each other and to
-    the default; rounding-level differences to 2 / 3 / 4), 5 = the role-specialised 128-row kernel (tests and probes)"""
+    the default; rounding-level differences to 2 / 3 / 4); any other value raises DsvgError"""
     _chk(x, packed_fwd_layer, b1f, b2, seed, out)
     assert x.dtype == torch.bfloat16 and x.dim() == 2 and x.shape[1] == 256 and x.is_contiguous()
     assert packed_fwd_layer.numel() == FFN_FWD_LAYER_ELEMS and packed_fwd_layer.is_contiguous()
@@ -1584,6 +1584,8 @@ def gs_layer_bwd(dx2, packed_bwd_layer, x, mean1, rstd1, qkv, x1, mean2, rstd2, 
                  dbeta1=None, want_dg=False):
     """backward of gs_layer_fwd with respect to x (include/dsvg.h) -> (dx, dx1 or None, dym, dpre, dx1m, dqkv, dgamma2,
     dbeta2, dgamma1, dbeta1): dym / dpre / dx1m / dqkv are the token-major operands of the four weight-gradient GEMMs.
+    want_dx1: test hook; the step passes False.  In the kernel it is one guarded store; the tests check dx1 itself and use it
+    as the comparator of dg at drop_p > 0, where dx1 cannot be recovered from dx1m.
     want_dg: one more result at the end, dg [n_seq, 256] = bcast_add_bwd(dx1, n_seq, S, drop_p, site0 + 2, seed) bit for bit
     (the per-sequence term's gradient, formed in the same launch)."""
     _chk(dx2, packed_bwd_layer, x, mean1, rstd1, qkv, x1, mean2, rstd2, h, gamma1, gamma2, key_mask, seed)

@@ -4,6 +4,8 @@
 # commit and the hash of the kernel source it was taken on.  FETCH_SIZE is calibrated on the inference variant of the same
 # kernel (known read bytes) instead of the blanket x2 of MI355X_MICROARCH.md, which holds for wide coalesced streaming reads.
 # usage: gpurun --timeout 600 -- 'bash scripts/gpu_ffn_traffic.sh'   -> gpurun_out/ffn_traffic.json (copy to profiles/)
+# A pass that fails or runs into its time limit ends the script: nothing more is started on the GPU behind it.
+set -e
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 export TMPDIR=/tmp PYTHONDONTWRITEBYTECODE=1
