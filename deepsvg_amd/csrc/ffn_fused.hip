@@ -83,9 +83,9 @@ __device__ __forceinline__ void drop2_mult8(const DropCtx& c, uint32_t h, int hi
     }
 }
 
-typedef unsigned short rs_u16x2 __attribute__((ext_vector_type(2)));
-typedef short rs_s16x2 __attribute__((ext_vector_type(2)));
-typedef float rs_f2 __attribute__((ext_vector_type(2)));
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+typedef short s16x2 __attribute__((ext_vector_type(2)));
+typedef float f2 __attribute__((ext_vector_type(2)));
 
 // Activation of a hidden tile on PACKED pairs (round 5; 5.5 instructions per pair instead of 19): the 16 accumulator values
 // of a lane -> the two B-operand fragments of G2.
@@ -96,40 +96,36 @@ typedef float rs_f2 __attribute__((ext_vector_type(2)));
 //   saturating subtraction clears exactly the dropped halves (2 x v_pk_sub_u16 clamp + v_pk_sub_u16).
 // The same draws as drop2_mult8 (ids in lane order); the scale is applied before instead of after the ReLU: results differ
 // from the scalar form by fp32 rounding order only.
-// bs (BIAS): the lane's 16 bias values ALREADY MULTIPLIED BY THE SCALE, element 4 q + e at bs[8 q + e] (LDS): the
+// bs: the lane's 16 bias values ALREADY MULTIPLIED BY THE SCALE, element 4 q + e at bs[8 q + e] (LDS): the
 // token-stationary kernels start their hidden accumulator from zero (an initial value would be 16 more live registers under
 // G2) and add the bias here, fused with the scale: v_pk_fma_f32.
-template <bool BIAS>
 __device__ __forceinline__ void ffn_act_packed(const float (&v)[16], const DropCtx& dh, uint32_t hh, uint32_t (&pk)[8],
-                                               const float* bs = nullptr) {
-    const rs_f2 sc2 = {dh.scale, dh.scale};
-    const rs_s16x2 zero = {0, 0};
+                                               const float* bs) {
+    const f2 sc2 = {dh.scale, dh.scale};
+    const s16x2 zero = {0, 0};
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        float4 bb = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (BIAS) bb = *reinterpret_cast<const float4*>(bs + 8 * q);
+        const float4 bb = *reinterpret_cast<const float4*>(bs + 8 * q);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int k = 2 * q + j;
-            rs_f2 a = rs_f2{v[2 * k], v[2 * k + 1]};
-            if (BIAS) a = __builtin_elementwise_fma(a, sc2, j ? rs_f2{bb.z, bb.w} : rs_f2{bb.x, bb.y});
-            else a = a * sc2;
-            pk[k] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(rs_s16x2, f2bf_pk(a[0], a[1])), zero));
+            const f2 a = __builtin_elementwise_fma(f2{v[2 * k], v[2 * k + 1]}, sc2, j ? f2{bb.z, bb.w} : f2{bb.x, bb.y});
+            pk[k] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, f2bf_pk(a[0], a[1])), zero));
         }
     }
     if (dh.on) {
-        const rs_u16x2 tpair = {(unsigned short)dh.thresh, (unsigned short)dh.thresh};
-        const rs_u16x2 z = {0, 0};
+        const u16x2 tpair = {(unsigned short)dh.thresh, (unsigned short)dh.thresh};
+        const u16x2 z = {0, 0};
         // (stage by stage over the 8 words, not word by word: back-to-back dependent packed operations cost a wait state each)
-        rs_u16x2 r[8];
+        u16x2 r[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) r[k] = __builtin_bit_cast(rs_u16x2, drop2_word(hh, k));
+        for (int k = 0; k < 8; ++k) r[k] = __builtin_bit_cast(u16x2, drop2_word(hh, k));
 #pragma unroll
         for (int k = 0; k < 8; ++k) r[k] = __builtin_elementwise_sub_sat(tpair, r[k]);
 #pragma unroll
         for (int k = 0; k < 8; ++k) r[k] = z - r[k];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) pk[k] = __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(rs_u16x2, pk[k]), r[k]));
+        for (int k = 0; k < 8; ++k) pk[k] = __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(u16x2, pk[k]), r[k]));
     }
 }
 
@@ -187,7 +183,7 @@ __device__ __forceinline__ void bwd_stamp(unsigned long long* d, int slot) {
 // without the affine part (folded into W1' / b1') -> the 16 B-operand fragments xf; TRAIN also stores xh and rstd.
 // The statistics come from the packed words (ln_stats_packed, fused_common.h: the prologue is instruction-issue-bound).
 // Called between the row loads and the first use of b1 / b2 (__syncthreads).
-template <bool TRAIN, bool SYNC = true>
+template <bool TRAIN>
 __device__ __forceinline__ void ffn_ln_rows(const bf16_t* __restrict__ x, int my_row, int half, bool st,
                                             bf16_t* __restrict__ xh_out, float* __restrict__ rstd_out, float eps,
                                             bf16x8 (&xf)[16]) {
@@ -195,7 +191,7 @@ __device__ __forceinline__ void ffn_ln_rows(const bf16_t* __restrict__ x, int my
     uint4 raw[16];
 #pragma unroll
     for (int ks = 0; ks < 16; ++ks) raw[ks] = *reinterpret_cast<const uint4*>(xr + 32 * ks);
-    if (SYNC) __syncthreads();  // b1 / b2 staged (the row loads above are in flight meanwhile)
+    __syncthreads();            // b1 / b2 staged (the row loads above are in flight meanwhile)
     float s, q, mean, rstd;
     ln_stats_packed(raw, s, q);
     ln_mean_rstd256(s, q, eps, mean, rstd);
@@ -330,7 +326,7 @@ __global__ __launch_bounds__(512, 2) void ffn_fwd_kernel(const bf16_t* __restric
 #pragma unroll
             for (int r = 0; r < 16; ++r) v[r] = hid[r];
             uint32_t pk[8];
-            ffn_act_packed<true>(v, dh, hh, pk, sb1 + CH * c + 4 * half);
+            ffn_act_packed(v, dh, hh, pk, sb1 + CH * c + 4 * half);
             Frag8 f0, f1;
             f0.u = make_uint4(pk[0], pk[1], pk[2], pk[3]);
             f1.u = make_uint4(pk[4], pk[5], pk[6], pk[7]);
@@ -570,7 +566,7 @@ __global__ __launch_bounds__(256, 2) void ffn_fwd_half_kernel(const bf16_t* __re
 #pragma unroll
             for (int r = 0; r < 16; ++r) v[r] = hid[r];
             uint32_t pk[8];
-            ffn_act_packed<true>(v, dh, hh, pk, sb1 + CH * c + 4 * half);
+            ffn_act_packed(v, dh, hh, pk, sb1 + CH * c + 4 * half);
             Frag8 f0, f1;
             f0.u = make_uint4(pk[0], pk[1], pk[2], pk[3]);
             f1.u = make_uint4(pk[4], pk[5], pk[6], pk[7]);
@@ -685,163 +681,12 @@ __global__ __launch_bounds__(256, 2) void ffn_fwd_half_kernel(const bf16_t* __re
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// backward, kernel 1 of 2: the hidden tile.  Per 32-token wave and hidden chunk c:
-//     pre  = W1'[chunk] . xh            (recomputed: the forward pass stores nothing but x)
-//     dh   = W2[:, chunk]^T . dym       (dym = dy * residual-dropout mask, replayed)
-//     h    = drop_h(relu(pre + b1')),  dpre = dh * [pre + b1' > 0] * drop_h mask
-// and writes, for the weight-gradient GEMMs and kernel 2: h and dpre (bf16 [T, 512], hidden columns in FRAGMENT ORDER:
-// position 32 c + 16 s + 8 b + 4 a + e holds unit 32 c + 16 s + 8 a + 4 b + e - exactly the 8 values a lane owns per K
-// step, so every store is one aligned 16-byte piece and kernel 2 reads its B operands back with one 16-byte load),
-// xh = (x - mean) * rstd and dym (bf16 [T, 256]).  The two 16-deep MFMA chains (pre, dh) are independent and issued
-// alternately, so no dependent MFMA sits right behind its predecessor's LDS read.
-// LDS ring: [W1' chunk | W2^T chunk] = the first 32 KiB of every 48 KiB backward chunk.
-// (stores are in flight inside the loop and vmcnt also counts them, out of order with respect to loads: every wait is 0)
-// ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(512, 2) void ffn_bwd_hidden_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy,
-                                                                const bf16_t* __restrict__ img, const float* __restrict__ b1,
-                                                                bf16_t* __restrict__ h_out, bf16_t* __restrict__ dpre_out,
-                                                                bf16_t* __restrict__ xh_out, bf16_t* __restrict__ dym_out,
-                                                                int M, float eps, float drop_p,
-                                                                const uint64_t* __restrict__ seed, uint32_t site_h,
-                                                                uint32_t site_r) {
-    constexpr int NBUF = 3;
-    extern __shared__ __attribute__((aligned(1024))) char smem[];      // [3 x 32 KiB | b1' (2 KiB)]
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const bool late = wave >= 4;
-    const int tok = lane & 31, half = lane >> 5;
-    const uint32_t lds0 = (uint32_t)(uintptr_t)DSVG_LDS_PTR(smem);
-    float* sb1 = reinterpret_cast<float*>(smem + NBUF * FWD_CHUNK);
-
-    const char* my_src = reinterpret_cast<const char*>(img) + wave * 4096 + lane * 16;
-    const uint32_t my_dst = __builtin_amdgcn_readfirstlane(lds0 + wave * 4096);
-    auto issue = [&](int c) { dma4(my_src + (size_t)c * BWD_CHUNK, my_dst + (uint32_t)(c % NBUF) * FWD_CHUNK); };
-    issue(0);
-    issue(1);
-    sb1[tid] = b1[tid];
-
-    const int row0 = blockIdx.x * TOK_PER_WG + wave * 32;
-    const int m = row0 + tok;
-    const bool live = m < M;
-    const int my_row = min(m, M - 1);
-    const DropCtx dh_ctx = drop_make(drop_p, seed, site_h);
-    const DropCtx dr_ctx = drop_make(drop_p, seed, site_r);
-
-    // ---- xh fragments (LayerNorm without the affine part, bit-identical to the forward kernel's) and their copy for the
-    // weight-gradient GEMM ----
-    bf16x8 xf[16];
-    ffn_ln_rows<true, false>(x, my_row, half, live, xh_out, nullptr, eps, xf);
-    // ---- dym fragments: dy with the residual dropout replayed (ids m * 256 + column, standard draws) ----------------------
-    bf16x8 df[16];
-    {
-        const char* dr = reinterpret_cast<const char*>(dy) + (size_t)my_row * (FD * 2) + half * 16;
-        char* dm_o = reinterpret_cast<char*>(dym_out) + (size_t)my_row * (FD * 2) + half * 16;
-        uint4 raw[16];
-#pragma unroll
-        for (int ks = 0; ks < 16; ++ks) raw[ks] = *reinterpret_cast<const uint4*>(dr + 32 * ks);
-#pragma unroll
-        for (int ks = 0; ks < 16; ++ks) {
-            Frag8 f;
-            if (dr_ctx.on) {
-                float v[8], mm[8];
-                unpack8(raw[ks], v);
-                drop_mult8(dr_ctx, (uint64_t)m * FD + 16 * ks + 8 * half, mm);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] *= mm[e];
-                f.u = pack8(v);
-                if (live) *reinterpret_cast<uint4*>(dm_o + 32 * ks) = f.u;
-            } else {
-                f.u = raw[ks];      // no dropout: dym == dy, the caller passes dy itself to the weight-gradient GEMM
-            }
-            df[ks] = f.v;
-        }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-
-    floatx16 pre, dh;
-    uint4 ring[4];
-    const char* lbase = smem + lane * 16;
-    auto slot_of = [&](int c) -> const char* { return lbase + (c % NBUF) * FWD_CHUNK; };
-    auto ld = [&](const char* p) -> uint4 { return *reinterpret_cast<const uint4*>(p); };
-    // vmcnt counts the h / dpre stores too, and stores retire out of order with respect to loads: the only safe wait is
-    // vmcnt(0).  It sits right behind the GEMMs of a chunk - BEFORE that chunk's stores are issued - so that it covers
-    // the DMA issued one GEMM phase earlier and the stores of the PREVIOUS chunk, which have had a whole GEMM phase to
-    // drain; the barrier itself then needs no wait (every wave confirmed its pieces of chunk k + 1 before reaching it).
-    auto landed = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
-    auto sync = [&](int k) {
-        __builtin_amdgcn_s_barrier();
-        if (k + 2 < NCH) issue(k + 2);
-    };
-    // fragment stream of a chunk in consumption order: W1'[0], W2T[0], W1'[1], W2T[1], ... (fragment n -> n / 2 + 16 (n & 1))
-    auto frag_at = [&](const char* sc, int n) -> const char* { return sc + ((n >> 1) + 16 * (n & 1)) * FRAG; };
-    auto GEMMS = [&](const char* sc, const char* sn) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { pre[r] = 0.f; dh[r] = 0.f; }
-#pragma unroll
-        for (int n = 0; n < 32; ++n) {
-            Frag8 a;
-            a.u = ring[n & 3];
-            if (n & 1) dh = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v, df[n >> 1], dh, 0, 0, 0);
-            else pre = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v, xf[n >> 1], pre, 0, 0, 0);
-            if (n + 4 < 32) ring[n & 3] = ld(frag_at(sc, n + 4));
-            else if (sn) ring[n & 3] = ld(frag_at(sn, n + 4 - 32));
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-    auto EPI = [&](int c) {
-        const uint64_t id0 = (uint64_t)m * FF + (uint32_t)(CH * c + 16 * half);
-        const uint32_t hh = dh_ctx.on ? drop2_group(dh_ctx, id0 >> 4) : 0u;
-        char* ho = reinterpret_cast<char*>(h_out) + (size_t)my_row * (FF * 2) + (CH * c + 8 * half) * 2;
-        char* po = reinterpret_cast<char*>(dpre_out) + (size_t)my_row * (FF * 2) + (CH * c + 8 * half) * 2;
-#pragma unroll
-        for (int ks2 = 0; ks2 < 2; ++ks2) {
-            float hv[8], pv[8], mm[8];
-            if (dh_ctx.on) drop2_mult8(dh_ctx, hh, ks2, mm);
-#pragma unroll
-            for (int qq = 0; qq < 2; ++qq) {
-                const int q = 2 * ks2 + qq;
-                const float4 bb = *reinterpret_cast<const float4*>(sb1 + CH * c + 8 * q + 4 * half);
-                const float bq[4] = {bb.x, bb.y, bb.z, bb.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float p = pre[4 * q + e] + bq[e];
-                    const float keep = dh_ctx.on ? mm[4 * qq + e] : 1.f;
-                    const bool act = p > 0.f;
-                    hv[4 * qq + e] = act ? p * keep : 0.f;
-                    pv[4 * qq + e] = act ? dh[4 * q + e] * keep : 0.f;
-                }
-            }
-            if (live) {
-                *reinterpret_cast<uint4*>(ho + 32 * ks2) = pack8(hv);
-                *reinterpret_cast<uint4*>(po + 32 * ks2) = pack8(pv);
-            }
-        }
-    };
-
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();           // chunks 0 and 1 (and b1') are in LDS
-    {
-        const char* s0 = slot_of(0);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) ring[i] = ld(frag_at(s0, i));
-    }
-    for (int c = 0; c < NCH; ++c) {
-        const char* sc = slot_of(c);
-        const char* sn = (c + 1 < NCH) ? slot_of(c + 1) : nullptr;
-        if (!late) sync(c);
-        GEMMS(sc, sn);
-        landed();
-        if (late) sync(c);
-        EPI(c);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// backward, kernel 2 of 2: dx = dy + LayerNorm'( dpre . W1' ).  Token-stationary like the forward kernel; the B operands
-// (dpre in fragment order, see kernel 1) come straight from global memory, one chunk ahead; W1'^T chunks (the last 16
-// KiB of every 48 KiB backward chunk) stream through a 4-slot LDS ring.  The LayerNorm backward needs no gamma (it is
-// inside W1'): dx = dy + rstd * (g - mean(g) - xh * mean(g * xh)), g = dxh, statistics over the row in registers.
+// backward: dx = dy + LayerNorm'( dpre . W1' ), the FFN backward's only kernel in this file (dpre comes from the gated GEMM over
+// the forward kernel's h, the weight gradients from the library's GEMMs + the finish kernels below).  Token-stationary like the
+// forward kernel; the B operands (dpre in fragment order, the layout of the forward kernel's h, see TRAIN above) come straight
+// from global memory, one chunk ahead; W1'^T chunks (the last 16 KiB of every 48 KiB backward chunk) stream through a 4-slot LDS
+// ring.  The LayerNorm backward needs no gamma (it is inside W1'): dx = dy + rstd * (g - mean(g) - xh * mean(g * xh)), g = dxh,
+// statistics over the row in registers.
 // ---------------------------------------------------------------------------------------------------------------------
 template <bool PROBE>       // (PROBE: the stamps below; the production instantiation carries none of their code - they cost it 33 spilled registers)
 __global__ __launch_bounds__(512, 2) void ffn_bwd_dx_kernel(const bf16_t* __restrict__ dpre, const bf16_t* __restrict__ x,
@@ -1190,29 +1035,6 @@ extern "C" int dsvg_ffn_fwd(const void* x, const void* packed_fwd_layer, const f
 /* development probe: buf = device buffer of (workgroups * 8 * 4) uint64 or NULL (off); see ffn_stamp */
 extern "C" int dsvg_ffn_debug_clock(void* buf) {
     g_ffn_dbg_host = (unsigned long long*)buf;
-    return 0;
-}
-
-extern "C" int dsvg_ffn_bwd(const void* x, const void* dy, const void* packed_bwd_layer, const float* b1_folded, void* h,
-                            void* dpre, void* xh, void* dym, void* dx, int64_t rows, float eps, float drop_p,
-                            uint32_t site_hidden, uint32_t site_res, const void* seed, void* stream) {
-    DSVG_CHECK_ARG(x && dy && packed_bwd_layer && b1_folded && h && dpre && xh && dx, "ffn_bwd: null pointer");
-    DSVG_CHECK_ARG(rows > 0 && rows < (1ll << 31) - TOK_PER_WG, "ffn_bwd: bad row count");
-    DSVG_CHECK_ARG(!(drop_p > 0.f) || (seed && dym), "ffn_bwd: dropout needs a seed and the dym buffer");
-    DSVG_CHECK_ARG((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)h | (uintptr_t)dpre | (uintptr_t)xh | (uintptr_t)dym |
-                     (uintptr_t)dx | (uintptr_t)packed_bwd_layer) & 15) == 0, "ffn_bwd: operands must be 16-byte aligned");
-    const int nb = (int)((rows + TOK_PER_WG - 1) / TOK_PER_WG);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t lds1 = 3 * FWD_CHUNK + 2048, lds2 = 4 * 16 * FRAG;
-    DSVG_ENSURE_LDS(ffn_bwd_hidden_kernel, lds1);
-    hipLaunchKernelGGL(ffn_bwd_hidden_kernel, dim3(nb), dim3(512), lds1, st, (const bf16_t*)x, (const bf16_t*)dy,
-                       (const bf16_t*)packed_bwd_layer, b1_folded, (bf16_t*)h, (bf16_t*)dpre, (bf16_t*)xh, (bf16_t*)dym,
-                       (int)rows, eps, drop_p, (const uint64_t*)seed, site_hidden, site_res);
-    DSVG_LAUNCH_CHECK("ffn_bwd (hidden)");
-    hipLaunchKernelGGL(ffn_bwd_dx_kernel<false>, dim3(nb), dim3(512), lds2, st, (const bf16_t*)dpre, (const bf16_t*)x,
-                       (const bf16_t*)dy, (const bf16_t*)packed_bwd_layer, (bf16_t*)dx, (int)rows, eps, (bf16_t*)nullptr, 0.f,
-                       (const uint64_t*)nullptr, 0u, 0, (unsigned long long*)nullptr);
-    DSVG_LAUNCH_CHECK("ffn_bwd (dx)");
     return 0;
 }
 

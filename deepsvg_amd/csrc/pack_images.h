@@ -65,7 +65,7 @@ __device__ __forceinline__ void ffn_slot(long long gid, const float* __restrict_
     } else {
         const int g = f - 32;
         dst = bwd + ((size_t)layer * FFN_NCH + c) * (FFN_BWD_CHUNK / 2) + (size_t)g * 512 + l * 8;
-        if (g < 16) {               // W1' chunk again (recomputation of the hidden tile)
+        if (g < 16) {               // W1' chunk again; it and the W2^T chunk have no reader (the image can shrink)
 #pragma unroll
             for (int e = 0; e < 8; ++e) { const int k = 16 * g + 8 * half + e; v[e] = W1[(size_t)(FFN_CH * c + i) * D + k] * ga[k]; }
         } else if (g < 32) {        // W2^T chunk, K step ks over the 256 outputs: A[i = hidden 32 c + i][k = out 16 ks + 8 half + e]

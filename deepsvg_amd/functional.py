@@ -950,8 +950,8 @@ class LayerFn(torch.autograd.Function):
                 # (dpre . W1' with the LayerNorm backward in its epilogue).  Each weight-gradient GEMM runs right
                 # behind the launch that produced its token-major operand (dym, dpre: 65 / 130 MB that are then still
                 # partly in the memory-side cache), not at the end
-                # (measured slower: the fully fused ops.ffn_bwd, which recomputes the hidden tile but writes h, dpre, xh AND dym,
-                # profiles/r02_ffn_microbench.log)
+                # (measured slower and since removed: the fully fused backward kernel, which recomputed the hidden tile but
+                # wrote h, dpre, xh AND dym, profiles/r02_ffn_microbench.log)
                 # (round 4, MI355X: the three launches below as ONE kernel - dsvg_ffn_bwd_one, the mirror image of ffn_fwd -
                 # were bit-identical and 13 % faster in isolation (93 -> 80 us at 63 k rows) but 0.4 % SLOWER inside the
                 # step, where dym already comes from the masked bcast_add_bwd and dpre is read back from the memory-side

@@ -41,8 +41,9 @@ extern "C" {
  * 9 (round 6): dg_ld argument of dsvg_bcast_add_bwd / dsvg_bcast_add_bwd_masked (dg as a column block of a wider buffer).
  * 10: dsvg_ffn_gate_dw2 added (the gated dpre GEMM and the dW2 split-K GEMM of the fused FFN backward as one launch).
  * 11: two-stage configs with paths of 65..256 tokens: dsvg_build_masks_lens, dsvg_pack_tokens_lens, dsvg_packed_mean_fwd /
- *     bwd, dsvg_attention_long_packed_fwd / bwd, dsvg_attention_long_mfma_fwd / bwd added. */
-#define DSVG_ABI_VERSION 11
+ *     bwd, dsvg_attention_long_packed_fwd / bwd, dsvg_attention_long_mfma_fwd / bwd added.
+ * 12: dsvg_ffn_bwd removed (the fully fused FFN backward: no caller since round 2; dsvg_ffn_bwd_dx is the FFN backward's kernel). */
+#define DSVG_ABI_VERSION 12
 
 const char* dsvg_last_error(void);
 int dsvg_version(void);
@@ -340,7 +341,8 @@ int dsvg_advance_step(int64_t* counter, uint64_t* seed, void* stream);
  * device code, csrc/pack_images.h), i.e. the `.to(bf16)` copies of the parameters an autocast forward of
  * deepsvg/model/model.py makes, laid out for the fused kernels.  n = elements of the flat buffers (a multiple of 8, both
  * 16-byte aligned).  A family with 0 layers is skipped; ffn_w2p, attn_bwd (only a backward pass reads it), counter and seed
- * may each be NULL.  offs tables as in the stand-alone calls. */
+ * may each be NULL (ffn_bwd, which only dsvg_ffn_bwd_dx reads, is required with the FFN family, as in dsvg_ffn_pack).
+ * offs tables as in the stand-alone calls. */
 int dsvg_pack_images(const float* flat_f32, void* flat_bf16, int64_t n,
                      const int64_t* ffn_offs, int32_t ffn_layers, void* ffn_fwd, void* ffn_bwd, float* ffn_b1f, void* ffn_w2p,
                      const int64_t* attn_offs, int32_t attn_layers, void* attn_img, void* attn_bwd,
@@ -558,7 +560,8 @@ int dsvg_assemble_batch(const int16_t* rows, int64_t n_rows, const int32_t* slot
  *                   `flat_f32`; offs = int64 device array [n_layers][5] of element offsets of (linear1.weight,
  *                   linear1.bias, linear2.weight, norm.weight, norm.bias).  The LayerNorm's affine part is folded into
  *                   linear1: W1' = W1 diag(gamma), b1' = b1 + W1 beta (b1_folded, fp32 [n_layers][512]).
- *                   packed_fwd [n_layers][16][32 KiB], packed_bwd [n_layers][16][48 KiB] (dsvg_ffn_pack_bytes(n, 0 | 1)).
+ *                   packed_fwd [n_layers][16][32 KiB], packed_bwd [n_layers][16][48 KiB] (dsvg_ffn_pack_bytes(n, 0 | 1));
+ *                   of a packed_bwd chunk [W1' | W2^T | W1'^T] only the last 16 KiB have a reader, dsvg_ffn_bwd_dx.
  *                   w2p (optional, bf16 [n_layers][256][512]): linear2.weight with its columns in fragment order, the B
  *                   operand of the unfused input-gradient GEMM dpre = dym . W2p.
  *   dsvg_ffn_fwd    x, y bf16 [rows, 256] (row stride 256); packed_fwd_layer / b1_folded = that layer's slices; b2 fp32;
@@ -578,21 +581,15 @@ int dsvg_ffn_pack(const float* flat_f32, const int64_t* offs, int32_t n_layers, 
 int dsvg_ffn_fwd(const void* x, const void* packed_fwd_layer, const float* b1_folded, const float* b2, void* y,
                  void* h_out, void* xh_out, float* rstd_out, int64_t rows, float eps, float drop_p,
                  uint32_t site_hidden, uint32_t site_res, const void* seed, int32_t stages, void* stream);
-/* Backward of the fused FFN sub-block (two launches; csrc/ffn_fused.hip):
- *   kernel 1 recomputes the hidden tile from x, replays both dropout masks and writes what the weight-gradient GEMMs
- *            need: h, dpre bf16 [rows, 512] with the hidden columns in FRAGMENT ORDER (position p(j) = j with bits 2 and 3
- *            swapped), xh = (x - mean) * rstd and dym = dy * residual-dropout mask, bf16 [rows, 256] (dym may be NULL
- *            when drop_p == 0: then dym == dy);
- *   kernel 2 dx = dy + LayerNorm'(dpre . W1').
+/* Backward of the fused FFN sub-block (csrc/ffn_fused.hip), from what a training dsvg_ffn_fwd stored (h, xh, rstd):
+ *   dym  = dy * residual-dropout mask (dsvg_drop_apply; dym == dy when drop_p == 0), bf16 [rows, 256];
+ *   dpre = (dym . W2p) gated by h > 0, x 1 / (1 - drop_p): one dsvg_gemm with gate = h, or dsvg_ffn_gate_dw2; bf16 [rows, 512]
+ *          with the hidden columns in FRAGMENT ORDER (position p(j) = j with bits 2 and 3 swapped), like h;
+ *   dx   = dy + LayerNorm'(dpre . W1'): dsvg_ffn_bwd_dx, the only reader of packed_bwd (its W1'^T part).
  * The caller then runs G2p = dym^T h [256, 512], G1p = dpre^T xh [512, 256] (+ row sums db1p, and db2 = colsum(dym))
  * with dsvg_gemm, and dsvg_ffn_wgrad_finish turns (G1p, db1p, G2p) into the gradients of linear1.weight / bias,
  * linear2.weight and of the LayerNorm's gamma / beta (w1 = fp32 master linear1.weight [512, 256]).
- * Replaces the autograd backward of deepsvg/model/layers/improved_transformer.py:51-53 / :138-140. */
-int dsvg_ffn_bwd(const void* x, const void* dy, const void* packed_bwd_layer, const float* b1_folded, void* h, void* dpre,
-                 void* xh, void* dym, void* dx, int64_t rows, float eps, float drop_p, uint32_t site_hidden,
-                 uint32_t site_res, const void* seed, void* stream);
-/* kernel 2 alone: dx = dy + LayerNorm'(dpre . W1') from a dpre (bf16 [rows, 512], fragment order) the caller produced
- * (training default: dpre = (dym . W2p) gated by the h the forward kernel stored, one dsvg_gemm).
+ * Replaces the autograd backward of deepsvg/model/layers/improved_transformer.py:51-53 / :138-140.
  * dx_masked (optional): a second output, dx with the dropout mask (drop_p, drop_site, ids row * 256 + column) replayed on
  * it - exactly dsvg_drop_apply(dx) - for the attention sub-block's backward, which starts from it */
 int dsvg_ffn_bwd_dx(const void* dpre, const void* x, const void* dy, const void* packed_bwd_layer, void* dx,

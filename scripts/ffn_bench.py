@@ -37,7 +37,8 @@ def main():
         flat[o + 262144 + 512:o + 262144 + 768] = 1.0
     flat = flat.to(DEV)
     offs = torch.tensor(offs, dtype=torch.int64, device=DEV)
-    pf, pb, b1f = ops.ffn_pack(flat, offs, 2)
+    w2p = torch.empty((2, 256, 512), dtype=torch.bfloat16, device=DEV)
+    pf, pb, b1f = ops.ffn_pack(flat, offs, 2, w2p=w2p)
     t_pack = timeit(lambda: ops.ffn_pack(flat, offs, 2, pf, pb, b1f))
     print(f"ffn_pack (2 layers): {t_pack:.1f} us")
     W1 = flat[8:8 + 131072].view(512, 256).to(torch.bfloat16)
@@ -53,8 +54,6 @@ def main():
         rows = 126976
         x = torch.randn(rows, 256, generator=g).to(DEV).to(torch.bfloat16)
         dy = torch.randn(rows, 256, generator=g).to(DEV).to(torch.bfloat16)
-        w2p = torch.empty((2, 256, 512), dtype=torch.bfloat16, device=DEV)
-        ops.ffn_pack(flat, offs, 2, pf, pb, b1f, w2p)
         for _ in range(3):
             ops.ffn_fwd(x, pl, b1f[0], b2, 1e-5, 0.1, 3, 4, seed)
             y, h, xh, rstd = ops.ffn_fwd(x, pl, b1f[0], b2, 1e-5, 0.1, 3, 4, seed, train=True)
@@ -85,7 +84,8 @@ def main():
         print(line, flush=True)
         if quick:
             continue
-        # ---- backward: fused (2 launches + 2 weight-gradient GEMMs + finish) vs the unfused sequence ----
+        # ---- backward: the step's sequence (drop_apply + gated GEMM + ffn_bwd_dx on the h / xh a training forward stored,
+        # then 2 weight-gradient GEMMs + finish) vs the unfused sequence ----
         dy = torch.randn(rows, 256, generator=g).to(DEV).to(torch.bfloat16)
         pbl = pb[:ops.FFN_BWD_LAYER_ELEMS]
         W1m = flat[8:8 + 131072].view(512, 256)
@@ -93,10 +93,13 @@ def main():
         g2p, g1p = torch.empty(256, 512, device=DEV), torch.empty(512, 256, device=DEV)
         db1p, db2 = torch.empty(512, device=DEV), torch.empty(256, device=DEV)
         s2, s1 = ops.split_k_for(256, 512, rows), ops.split_k_for(512, 256, rows)
+        _, hp, xh, _ = ops.ffn_fwd(x, pl, b1f[0], b2, 1e-5, 0.1, 3, 4, seed, train=True)
 
         def fused_bwd_kernels(p=0.1):
-            return ops.ffn_bwd(x, dy, pbl, b1f[0], 1e-5, p, 3, 4, seed)
-        dx, hp, dpre, xh, dym = fused_bwd_kernels()
+            dym = ops.drop_apply(dy, p, 4, seed)
+            dpre = ops.gemm(dym, w2p[0], b_kc=False, gate=hp, gate_scale=1.0 / (1.0 - p))
+            return ops.ffn_bwd_dx(dpre, x, dy, pbl), dpre, dym
+        dx, dpre, dym = fused_bwd_kernels()
 
         def fused_wgrad():
             ops.gemm(dym, hp, a_kc=False, b_kc=False, out=g2p, split_k=s2, rowsum=db2)
@@ -116,7 +119,7 @@ def main():
             ops.layernorm_bwd(dxn, x, mean, rstd, gamma, res=dy, dgamma=dg, dbeta=dbt)
         t1, t2, t3 = timeit(fused_bwd_kernels), timeit(fused_wgrad), timeit(unfused_bwd)
         fl = 8.0 * 256 * 512 * rows
-        print(f"   backward rows {rows:7d}: fused dX kernels {t1:7.1f} us + wgrad GEMMs/finish {t2:7.1f} us = {t1 + t2:7.1f} us "
+        print(f"   backward rows {rows:7d}: drop_apply + gated GEMM + ffn_bwd_dx {t1:7.1f} us + wgrad GEMMs/finish {t2:7.1f} us = {t1 + t2:7.1f} us "
               f"({fl / (t1 + t2) * 1e-6:5.0f} TF/s algorithmic) | unfused {t3:7.1f} us ({fl / t3 * 1e-6:5.0f} TF/s)", flush=True)
 
 

@@ -437,9 +437,9 @@ def test_hierarch_outputs_feed_straight_back_for_a_batch(emulated_ops):
 
 
 def test_fused_ffn_path_matches_unfused_with_emulated_ops(emulated_ops):
-    """bf16 compute: every layer's FFN runs through ffn_fwd / ffn_bwd / wgrad_finish (LayerNorm folded into the packed
-    linear1, fragment-ordered weight gradients) - the wiring must reproduce the unfused layer's loss and gradients up
-    to bf16 rounding, including the live-prefix backward of the second decoder stage"""
+    """bf16 compute: every layer's FFN runs through ffn_fwd / gated GEMM / ffn_bwd_dx / wgrad_finish (LayerNorm folded
+    into the packed linear1, fragment-ordered weight gradients) - the wiring must reproduce the unfused layer's loss and
+    gradients up to bf16 rounding, including the live-prefix backward of the second decoder stage"""
     from deepsvg_amd.synthetic import make_batch
     import deepsvg_amd.functional as Fn
     cfg = H.build_cfg("hier")

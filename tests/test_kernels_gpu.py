@@ -1070,19 +1070,31 @@ def test_ffn_fwd_equals_unfused_kernels(gpu_device):
     _close(y, want, 1.2e-2, "fused vs unfused FFN")
 
 
+def _ffn_step_bwd(x, dy, pf_layer, pb_layer, b1f_layer, b2, w2p_layer, drop_p, site_h, site_r, seed):
+    """the FFN sub-block's backward as a training step runs it: ffn_fwd(train=True) for h / xh, then drop_apply -> gated GEMM
+    on W2p -> ffn_bwd_dx.  -> (dx, h, dpre, xh, dym), h / dpre in fragment order (the tuple R.ffn_bwd returns)"""
+    _, h, xh, _ = ops.ffn_fwd(x, pf_layer, b1f_layer, b2, 1e-5, drop_p, site_h, site_r, seed, train=True)
+    dym = ops.drop_apply(dy, drop_p, site_r, seed)
+    dpre = ops.gemm(dym, w2p_layer, b_kc=False, gate=h, gate_scale=1.0 / (1.0 - drop_p))
+    dx = ops.ffn_bwd_dx(dpre, x, dy, pb_layer)
+    return dx, h, dpre, xh, dym
+
+
 @pytest.mark.parametrize("rows", [256, 1000, 4096 + 37])
 @pytest.mark.parametrize("drop_p", [0.0, 0.1])
 def test_ffn_bwd_matches_reference(gpu_device, rows, drop_p):
-    """the two backward launches against the restatement: dx, and the operands handed to the weight-gradient GEMMs
-    (h / dpre in fragment order, xh, dym), with both dropout masks replayed from the forward's ids"""
+    """the step's backward sequence (_ffn_step_bwd: training forward, drop_apply, gated GEMM, ffn_bwd_dx) against the
+    restatement: dx, and the operands handed to the weight-gradient GEMMs (h / dpre in fragment order, xh, dym), with both
+    dropout masks replayed from the forward's ids"""
     flat, offs, x, b2 = _ffn_setup(rows, seed=rows + 1)
-    pf, pb, b1f = ops.ffn_pack(flat, offs, 2)
+    w2p = torch.empty((2, 256, 512), dtype=torch.bfloat16, device=DEV)
+    pf, pb, b1f = ops.ffn_pack(flat, offs, 2, w2p=w2p)
     _, epb, eb1f = R.ffn_pack(flat, offs, 2)
     g = torch.Generator(device="cpu").manual_seed(rows)
     dy = torch.randn(rows, 256, generator=g).to(DEV).to(torch.bfloat16)
     seed = _seed_tensor(0x0123456789ABCDEF)
     sl = slice(ops.FFN_BWD_LAYER_ELEMS, 2 * ops.FFN_BWD_LAYER_ELEMS)
-    got = ops.ffn_bwd(x, dy, pb[sl], b1f[1], 1e-5, drop_p, 403, 404, seed)
+    got = _ffn_step_bwd(x, dy, pf[ops.FFN_FWD_LAYER_ELEMS:], pb[sl], b1f[1], b2, w2p[1], drop_p, 403, 404, seed)
     want = R.ffn_bwd(x, dy, epb[sl], eb1f[1], 1e-5, drop_p, 403, 404, seed)
     # ReLU gates of units whose pre-activation is within rounding of zero may differ between kernel and restatement
     # (a different fp32 summation order): compare h / dpre where both agree on the gate, and bound the disagreements
@@ -1195,7 +1207,8 @@ def test_ffn_wgrad_finish_and_full_gradients(gpu_device):
     dgamma, dbeta"""
     rows = 3000
     flat, offs, x, b2 = _ffn_setup(rows, seed=5)
-    pf, pb, b1f = ops.ffn_pack(flat, offs, 2)
+    w2p = torch.empty((2, 256, 512), dtype=torch.bfloat16, device=DEV)
+    pf, pb, b1f = ops.ffn_pack(flat, offs, 2, w2p=w2p)
     W1, b1, W2, gamma, beta = (t.clone().requires_grad_(True) for t in _ffn_params(flat, offs, 0))
     g = torch.Generator(device="cpu").manual_seed(9)
     dy = torch.randn(rows, 256, generator=g).to(DEV).to(torch.bfloat16)
@@ -1203,7 +1216,8 @@ def test_ffn_wgrad_finish_and_full_gradients(gpu_device):
     xn = torch.nn.functional.layer_norm(xf, (256,), gamma, beta, 1e-5)
     yref = xf + torch.relu(xn @ W1.t() + b1) @ W2.t() + b2
     yref.backward(dy.float())
-    dx, h, dpre, xh, dym = ops.ffn_bwd(x, dy, pb[:ops.FFN_BWD_LAYER_ELEMS], b1f[0])
+    dx, h, dpre, xh, dym = _ffn_step_bwd(x, dy, pf[:ops.FFN_FWD_LAYER_ELEMS], pb[:ops.FFN_BWD_LAYER_ELEMS], b1f[0], b2,
+                                         w2p[0], 0.0, 0, 0, None)
     g2p = torch.empty(256, 512, device=DEV)
     g1p = torch.empty(512, 256, device=DEV)
     db1p, db2 = torch.empty(512, device=DEV), torch.empty(256, device=DEV)
@@ -1244,8 +1258,13 @@ def test_ffn_wgrad_finish_and_full_gradients(gpu_device):
 @pytest.mark.parametrize("drop_p", [0.0, 0.1])
 def test_ffn_training_path_matches_reference(gpu_device, drop_p):
     """the default training path: forward kernel with train=True (stores h in fragment order + xh), then in the backward
-    pass drop_apply -> gated GEMM on W2p -> ffn_bwd_dx; every step against its restatement, and end to end against the
-    fully fused backward kernels (same dx up to rounding)"""
+    pass drop_apply -> gated GEMM on W2p -> ffn_bwd_dx; every step against its restatement on the kernel's own h.
+    The end-to-end comparison with the fully fused backward kernel went with that kernel: dpre, dx and h of this very path
+    are held against the independent restatement R.ffn_bwd by test_ffn_bwd_matches_reference (six cases), dym is bit-equal to
+    the restatement below.  The one assertion without a successor is the bit-equality of the two kernels' xh (two
+    instantiations of one inline function, one of them deleted): xh keeps its 1.5e-2 bound against the restatement in
+    test_ffn_bwd_matches_reference - not bit-equal there, the kernel takes sum / sum of squares where torch takes a two-pass
+    variance - and its bit-equality across the forward variants stays in test_ffn_fwd_packed_variant."""
     rows = 2000
     flat, offs, x, b2 = _ffn_setup(rows, seed=21)
     w2p = torch.empty((2, 256, 512), dtype=torch.bfloat16, device=DEV)
@@ -1269,17 +1288,6 @@ def test_ffn_training_path_matches_reference(gpu_device, drop_p):
     assert torch.equal(dym, edym)
     _close(dpre, edpre, 1.5e-2, "training path dpre")
     _close(dx, edx, 2e-2, "training path dx")
-    # and against the fully fused backward (which recomputes h and replays the hidden mask itself)
-    dx_f, h_f, dpre_f, xh_f, dym_f = ops.ffn_bwd(x, dy, pbl, b1f[0], 1e-5, drop_p, 403, 404, seed)
-    # (the backward kernel recomputes h with the scalar activation code, the forward default is the packed one: the same
-    # draws, values within fp32 summation order before the bf16 rounding)
-    assert torch.equal(xh_f, xh)
-    assert (((h_f != 0) != (h != 0)).float().mean().item()) < 1e-4
-    _close(h_f, h, 8e-3, "recomputed h vs the forward kernel's")
-    if drop_p > 0:
-        assert torch.equal(dym_f, dym)
-    _close(dpre_f, dpre, 1.5e-2, "fused vs training-path dpre")
-    _close(dx_f, dx, 2e-2, "fused vs training-path dx")
 
 
 def _attn_setup(seed=0, n_layers=2):

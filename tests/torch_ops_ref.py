@@ -858,6 +858,10 @@ def _ffn_frag_perm(device):
 
 
 def ffn_bwd(x, dy, packed_bwd_layer, b1f, eps=1e-5, drop_p=0.0, site_hidden=0, site_res=0, seed=None):
+    """the FFN sub-block's backward end to end, i.e. what the step's sequence ffn_fwd(train) -> drop_apply -> gated GEMM ->
+    ffn_bwd_dx computes, restated from x and dy alone (h recomputed, both dropout masks replayed): -> (dx, h, dpre, xh, dym),
+    h / dpre in fragment order.  No ops entry point of this name exists (the fully fused kernel is removed); the GPU tests
+    compare the step's sequence against it"""
     W1, W2 = _ffn_weights(packed_bwd_layer)
     rows = x.shape[0]
     xh, mean, rstd = _ffn_normalise(x, eps)
