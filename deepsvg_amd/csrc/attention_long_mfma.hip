@@ -18,12 +18,8 @@
 // from HBM that the backward pass does not stage anyway, and it costs 4 MFMAs per 32 x 32 tile.
 // Dropout draws the element ids of every other attention kernel: row (b H + h) S + i with S the padded length in both
 // layouts, key block j >> 5, attn_drop_key(.., j) (dsvg_common.h).
-#include "dsvg_common.h"
+#include "mfma_frag.h"
 #include "../../include/dsvg.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short shortx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
@@ -32,37 +28,9 @@ constexpr int NW = LT / 64;      // waves
 constexpr int TLD = 40;          // LDS row stride (elements) of a 32-column slab: 80 bytes, 16-byte aligned rows
 constexpr int MAX_S = 256;
 
-union F8 {
-    bf16x8 v;
-    shortx4 h[2];
-    uint4 u;
-};
-
-__device__ __forceinline__ int rowmap(int r, int h2) { return (r & 3) + 8 * (r >> 2) + 4 * h2; }
-
-// B / A operand of a 32x32x16 MFMA from a row-major slab: row `row`, columns 16 step + 8 h2 .. + 7
-__device__ __forceinline__ bf16x8 row_frag(const bf16_t* img, int row, int step, int h2) {
-    F8 f;
-    f.u = *reinterpret_cast<const uint4*>(&img[row * TLD + 16 * step + 8 * h2]);
-    return f.v;
-}
-// A[i = column c (lane&31)][k-slot e] = img[row(8*ks + e, h2)][c]: two hardware-transposed 4x16 reads
-__device__ __forceinline__ bf16x8 col_frag(const bf16_t* img, int ks, int lane) {
-    const int g = lane >> 4, q16 = lane & 15;
-    const int row = 16 * ks + 4 * (g >> 1) + (q16 >> 2);
-    const int col = 16 * (g & 1) + 4 * (q16 & 3);
-    F8 f;
-    f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((shortx4 __attribute__((address_space(3)))*)(&img[row * TLD + col]));
-    f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((shortx4 __attribute__((address_space(3)))*)(&img[(row + 8) * TLD + col]));
-    return f.v;
-}
-__device__ __forceinline__ bf16x8 pack_regs(const float (&p)[16], int ks) {
-    F8 f;
-    f.u = make_uint4(f2bf_pk(p[8 * ks + 0], p[8 * ks + 1]), f2bf_pk(p[8 * ks + 2], p[8 * ks + 3]),
-                     f2bf_pk(p[8 * ks + 4], p[8 * ks + 5]), f2bf_pk(p[8 * ks + 6], p[8 * ks + 7]));
-    return f.v;
-}
-// lane holds v[r] = X[row][d = rowmap(r, h2)]: four 8-byte pieces of the row's 32 columns
+// row_frag / col_frag (on a [..][TLD] slab: ld = TLD, col0 = 0) / pack_regs: mfma_frag.h
+// lane holds v[r] = X[row][d = rowmap(r, h2)]: four 8-byte pieces of the row's 32 columns.  (Not stage_rows of mfma_frag.h on
+// the row pointer: the compiler schedules the address of that form differently.)
 __device__ __forceinline__ void store_rowmap(bf16_t* dst_row, int h2, const floatx16& v) {
 #pragma unroll
     for (int c = 0; c < 4; ++c)
@@ -131,7 +99,7 @@ __global__ __launch_bounds__(LT) void attn_long_mfma_fwd_kernel(const bf16_t* __
     for (int qt = wave; qt < nqt; qt += NW) {
         const int qi = 32 * qt + li;
         const bf16_t* qrow = src + (size_t)min(qi, nq - 1) * 3 * d;
-        F8 qf[2];
+        Frag8 qf[2];
 #pragma unroll
         for (int step = 0; step < 2; ++step) qf[step].u = *reinterpret_cast<const uint4*>(qrow + 16 * step + 8 * h2);
         const uint64_t drow = ((uint64_t)b * H + h) * S + qi;
@@ -144,7 +112,7 @@ __global__ __launch_bounds__(LT) void attn_long_mfma_fwd_kernel(const bf16_t* __
             zero16(st);
 #pragma unroll
             for (int step = 0; step < 2; ++step)
-                st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(kimg, li, step, h2), qf[step].v, st, 0, 0, 0);
+                st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(kimg, TLD, li, 0, step, h2), qf[step].v, st, 0, 0, 0);
             // st[r] = q_qi . k_(32 kt + rowmap(r, h2))
             float p[16];
             float mt = -INFINITY;
@@ -175,7 +143,7 @@ __global__ __launch_bounds__(LT) void attn_long_mfma_fwd_kernel(const bf16_t* __
             const bf16_t* vimg = Vs + kt * 32 * TLD;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
-                ot = __builtin_amdgcn_mfma_f32_32x32x16_bf16(col_frag(vimg, ks, lane), pack_regs(p, ks), ot, 0, 0, 0);
+                ot = __builtin_amdgcn_mfma_f32_32x32x16_bf16(col_frag(vimg, TLD, 0, ks, lane), pack_regs(p, ks), ot, 0, 0, 0);
         }
         // ot[r] = O[q = qi][d = rowmap(r, h2)] (unnormalised)
         const float inv = l > 0.f ? 1.f / l : 0.f;
@@ -235,8 +203,8 @@ __global__ __launch_bounds__(LT) void attn_long_mfma_bwd_kernel(const bf16_t* __
             zero16(dp);
 #pragma unroll
             for (int step = 0; step < 2; ++step) {
-                st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(kimg, li, step, h2), row_frag(qimg, li, step, h2), st, 0, 0, 0);
-                dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(vimg, li, step, h2), row_frag(gimg, li, step, h2), dp, 0, 0, 0);
+                st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(kimg, TLD, li, 0, step, h2), row_frag(qimg, TLD, li, 0, step, h2), st, 0, 0, 0);
+                dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(vimg, TLD, li, 0, step, h2), row_frag(gimg, TLD, li, 0, step, h2), dp, 0, 0, 0);
             }
             float mt = -INFINITY;
 #pragma unroll
@@ -274,8 +242,8 @@ __global__ __launch_bounds__(LT) void attn_long_mfma_bwd_kernel(const bf16_t* __
             zero16(dp);
 #pragma unroll
             for (int step = 0; step < 2; ++step) {
-                st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(kimg, li, step, h2), row_frag(qimg, li, step, h2), st, 0, 0, 0);
-                dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(vimg, li, step, h2), row_frag(gimg, li, step, h2), dp, 0, 0, 0);
+                st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(kimg, TLD, li, 0, step, h2), row_frag(qimg, TLD, li, 0, step, h2), st, 0, 0, 0);
+                dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(vimg, TLD, li, 0, step, h2), row_frag(gimg, TLD, li, 0, step, h2), dp, 0, 0, 0);
             }
             const uint32_t hrow = dc.on ? attn_drop_row(dc, hbase + qi, (uint32_t)kt) : 0u;
             float g[16];
@@ -288,7 +256,7 @@ __global__ __launch_bounds__(LT) void attn_long_mfma_bwd_kernel(const bf16_t* __
             }
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
-                dq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(col_frag(kimg, ks, lane), pack_regs(g, ks), dq, 0, 0, 0);
+                dq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(col_frag(kimg, TLD, 0, ks, lane), pack_regs(g, ks), dq, 0, 0, 0);
         }
         if (h2 == 0) {
             lse_s[qi] = lse;
@@ -317,8 +285,8 @@ __global__ __launch_bounds__(LT) void attn_long_mfma_bwd_kernel(const bf16_t* __
                 zero16(dp2);
 #pragma unroll
                 for (int step = 0; step < 2; ++step) {
-                    s2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(qimg, li, step, h2), row_frag(kimg, li, step, h2), s2, 0, 0, 0);
-                    dp2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(gimg, li, step, h2), row_frag(vimg, li, step, h2), dp2, 0, 0, 0);
+                    s2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(qimg, TLD, li, 0, step, h2), row_frag(kimg, TLD, li, 0, step, h2), s2, 0, 0, 0);
+                    dp2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(gimg, TLD, li, 0, step, h2), row_frag(vimg, TLD, li, 0, step, h2), dp2, 0, 0, 0);
                 }
                 // s2[r] = q_(32 qt + rowmap(r, h2)) . k_kj
                 float pv[16], gv[16];
@@ -333,8 +301,8 @@ __global__ __launch_bounds__(LT) void attn_long_mfma_bwd_kernel(const bf16_t* __
                 }
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
-                    dk = __builtin_amdgcn_mfma_f32_32x32x16_bf16(col_frag(qimg, ks, lane), pack_regs(gv, ks), dk, 0, 0, 0);
-                    dv = __builtin_amdgcn_mfma_f32_32x32x16_bf16(col_frag(gimg, ks, lane), pack_regs(pv, ks), dv, 0, 0, 0);
+                    dk = __builtin_amdgcn_mfma_f32_32x32x16_bf16(col_frag(qimg, TLD, 0, ks, lane), pack_regs(gv, ks), dk, 0, 0, 0);
+                    dv = __builtin_amdgcn_mfma_f32_32x32x16_bf16(col_frag(gimg, TLD, 0, ks, lane), pack_regs(pv, ks), dv, 0, 0, 0);
                 }
             }
         }

@@ -15,13 +15,9 @@
 // ~20 MFMAs and a few hundred VALU ops per head instead of ~7000 FMAs per lane in the VALU kernel
 // (attention.hip, kept for fp32 and for the 8-token group stages); the kernel is HBM-bound.
 // Replaces deepsvg/model/layers/functional.py:168,197-248 and its autograd backward.
-#include "dsvg_common.h"
+#include "mfma_frag.h"
 #include "pack_images.h"
 #include "../../include/dsvg.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short shortx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
@@ -30,45 +26,7 @@ constexpr int W = HG * 32;       // columns of one q/k/v slab
 constexpr int LD = 3 * W + 8;    // row stride of the qkv image (elements); 388 dwords == 4 (mod 64)
 constexpr int LDO = W + 8;       // row stride of the dO image
 
-union F8 {
-    bf16x8 v;
-    shortx4 h[2];
-    uint4 u;
-};
-
-__device__ __forceinline__ int rowmap(int r, int h2) { return (r & 3) + 8 * (r >> 2) + 4 * h2; }
-
-__device__ __forceinline__ bf16x8 row_frag(const bf16_t* img, int ld, int row, int col0, int step, int h2) {
-    F8 f;
-    f.u = *reinterpret_cast<const uint4*>(&img[row * ld + col0 + 16 * step + 8 * h2]);
-    return f.v;
-}
-// A[i = column c (lane&31)][k-slot e] = img[row(8*ks + e, h2)][col0 + c]: two hardware-transposed 4x16 reads
-__device__ __forceinline__ bf16x8 col_frag(const bf16_t* img, int ld, int col0, int ks, int lane) {
-    const int g = lane >> 4, q16 = lane & 15;
-    const int row = 16 * ks + 4 * (g >> 1) + (q16 >> 2);
-    const int col = col0 + 16 * (g & 1) + 4 * (q16 & 3);
-    F8 f;
-    f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((shortx4 __attribute__((address_space(3)))*)(&img[row * ld + col]));
-    f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((shortx4 __attribute__((address_space(3)))*)(&img[(row + 8) * ld + col]));
-    return f.v;
-}
-__device__ __forceinline__ bf16x8 pack_regs(const float (&p)[16], int ks) {
-    F8 f;
-    f.u = make_uint4(f2bf_pk(p[8 * ks + 0], p[8 * ks + 1]), f2bf_pk(p[8 * ks + 2], p[8 * ks + 3]),
-                     f2bf_pk(p[8 * ks + 4], p[8 * ks + 5]), f2bf_pk(p[8 * ks + 6], p[8 * ks + 7]));
-    return f.v;
-}
-// lane holds out[row = lane&31][d = rowmap(r, h2)]: four 8-byte pieces per lane into the staging image
-__device__ __forceinline__ void stage_rows(bf16_t* img, int ld, int row, int col0, int h2, const floatx16& v) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        uint2 t;
-        t.x = f2bf_pk(v[4 * c + 0], v[4 * c + 1]);
-        t.y = f2bf_pk(v[4 * c + 2], v[4 * c + 3]);
-        *reinterpret_cast<uint2*>(&img[row * ld + col0 + 8 * c + 4 * h2]) = t;
-    }
-}
+// row_frag / col_frag / pack_regs / stage_rows / store_image: mfma_frag.h
 
 // 32 rows x W columns of up to four slabs -> LDS, 16-byte pieces, rows [S,32) zero-filled.  W = 256: 1024 pieces per
 // slab = 2 per thread.  All loads are issued before the first use, from row-clamped addresses with the zero selected
@@ -103,14 +61,6 @@ __device__ __forceinline__ void load_slabs(const SlabSrc (&sl)[NS], int S) {
             *reinterpret_cast<uint4*>(sl[n].dst + r * sl[n].ld_dst + 8 * c) = r < S ? v[n][k] : make_uint4(0u, 0u, 0u, 0u);
         }
 }
-__device__ __forceinline__ void store_slab(bf16_t* dst, long long ld_dst, const bf16_t* src, int ld_src, int S, int cols) {
-    const int cpr = cols / 8;
-    for (int idx = threadIdx.x; idx < S * cpr; idx += 512) {
-        const int r = idx / cpr, c = idx % cpr;
-        *reinterpret_cast<uint4*>(dst + r * ld_dst + 8 * c) = *reinterpret_cast<const uint4*>(src + r * ld_src + 8 * c);
-    }
-}
-
 // pad rows [row_begin, row_end) of one column slab <- 0 (packed layout, see attention.hip)
 __device__ __forceinline__ void zero_slab_rows(bf16_t* dst, long long ld, long long row_begin, long long row_end, int cols) {
     const int cpr = cols / 8;
@@ -231,7 +181,7 @@ __global__ __launch_bounds__(512) void attn_fwd_mfma_kernel(const bf16_t* __rest
     // ot[r] = O[q = li][d = rowmap(r,h2)]; the head's q slab is dead: reuse it as the output staging slab
     stage_rows(tile, LD, li, qc, h2, ot);
     __syncthreads();
-    store_slab(out + (size_t)row0 * d + (size_t)hg * W, (long long)d, tile, LD, S, W);
+    store_image(out + (size_t)row0 * d + (size_t)hg * W, (long long)d, tile, LD, 0, S, W);
 }
 
 // FO (8 heads, d_model 256): `dout` is the gradient of the attention block's OUTPUT PROJECTION result with the residual
@@ -288,7 +238,7 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_mfma_kernel(const bf16_t* __r
 
     const bf16_t* src = qkv + (size_t)row0 * 3 * d + (size_t)hg * W;
     // FO: the first half of this head's Wo^T fragments, issued ahead of the tile loads (L2-resident: 8 KiB per head)
-    F8 wa[8];
+    Frag8 wa[8];
     const uint4* wp = FO ? reinterpret_cast<const uint4*>(wo_img) + (size_t)(hh * 16) * 64 + lane : nullptr;
     if (FO) {
 #pragma unroll
@@ -460,7 +410,7 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_mfma_kernel(const bf16_t* __r
     for (int r = 0; r < 16; ++r) { dk[r] = 0.f; dv[r] = 0.f; }
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-        F8 fg, fp;
+        Frag8 fg, fp;
         fg.u = make_uint4(gp[4 * ks], gp[4 * ks + 1], gp[4 * ks + 2], gp[4 * ks + 3]);
         fp.u = make_uint4(pp[4 * ks], pp[4 * ks + 1], pp[4 * ks + 2], pp[4 * ks + 3]);
         dk = __builtin_amdgcn_mfma_f32_32x32x16_bf16(col_frag(tile, LD, qc, ks, lane), fg.v, dk, 0, 0, 0);
@@ -475,9 +425,9 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_mfma_kernel(const bf16_t* __r
     stage_rows(tile, LD, li, vc, h2, dv);
     __syncthreads();
     bf16_t* dst = dqkv + (size_t)row0 * 3 * d + (size_t)hg * W;
-    store_slab(dst, 3LL * d, tile, LD, S, W);
-    store_slab(dst + d, 3LL * d, tile + W, LD, S, W);
-    store_slab(dst + 2 * d, 3LL * d, tile + 2 * W, LD, S, W);
+    store_image(dst, 3LL * d, tile, LD, 0, S, W);
+    store_image(dst + d, 3LL * d, tile + W, LD, 0, S, W);
+    store_image(dst + 2 * d, 3LL * d, tile + 2 * W, LD, 0, S, W);
 }
 
 }  // namespace

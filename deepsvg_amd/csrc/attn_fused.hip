@@ -27,7 +27,6 @@
 #include "pack_images.h"
 #include "../../include/dsvg.h"
 
-typedef short shortx4 __attribute__((ext_vector_type(4)));
 typedef float af2 __attribute__((ext_vector_type(2)));
 typedef unsigned short au16x2 __attribute__((ext_vector_type(2)));
 
@@ -44,7 +43,6 @@ constexpr int VLD = 32;                 // row stride (elements) of the per-wave
 constexpr int SMALL_LDS = (768 + 256 + 256 + 256) * 4;      // in_proj bias | out_proj bias | gamma | beta
 constexpr int STAGE_LDS = TILES_PER_WG * 32 * VLD * 2;
 
-using dsvg_pack::rowmap;
 static_assert(dsvg_pack::ATTN_IMG_FRAGS == IMG_FRAGS && dsvg_pack::D == AD && dsvg_pack::H == AH, "pack_images.h restates these");
 // byte offset of chunk c in the layer image; chunks 2 h + 1 (v of head h) have 16 fragments, all others 32
 __device__ __forceinline__ int chunk_off(int c) {
@@ -55,18 +53,6 @@ __device__ __forceinline__ int chunk_off(int c) {
 __global__ __launch_bounds__(256) void attn_pack_kernel(const float* __restrict__ flat, const int64_t* __restrict__ offs,
                                                         int n_layers, bf16_t* __restrict__ img) {
     dsvg_pack::attn_slot((long long)blockIdx.x * 256 + threadIdx.x, flat, offs, n_layers, img);
-}
-
-// A[i = column c (lane & 31)][K slot e] = img[row rowmap(8 ks + e, lane >> 5)][col0 + c]: two hardware-transposed 4 x 16
-// reads (the same access attention_mfma.hip uses for V^T)
-__device__ __forceinline__ bf16x8 col_frag(const bf16_t* img, int ld, int col0, int ks, int lane) {
-    const int g = lane >> 4, q16 = lane & 15;
-    const int row = 16 * ks + 4 * (g >> 1) + (q16 >> 2);
-    const int col = col0 + 16 * (g & 1) + 4 * (q16 & 3);
-    union { bf16x8 v; shortx4 h[2]; } f;
-    f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((shortx4 __attribute__((address_space(3)))*)(&img[row * ld + col]));
-    f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((shortx4 __attribute__((address_space(3)))*)(&img[(row + 8) * ld + col]));
-    return f.v;
 }
 
 // The staging tile's swizzle: 64-byte rows, the eight 8-byte granules of row r stored at granule ^ stg_swz(r).
@@ -87,7 +73,7 @@ __device__ __forceinline__ bf16x8 col_frag_swz(const bf16_t* img, int ks, int la
     const int gran = 4 * (g & 1) + (q16 & 3);                      // 8-byte granule of the row
     const int off = row * VLD + 4 * (gran ^ stg_swz(row));
     const int off8 = (row + 8) * VLD + 4 * (gran ^ stg_swz(row + 8));
-    union { bf16x8 v; shortx4 h[2]; } f;
+    Frag8 f;
     f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((shortx4 __attribute__((address_space(3)))*)(&img[off]));
     f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((shortx4 __attribute__((address_space(3)))*)(&img[off8]));
     return f.v;

@@ -3,7 +3,7 @@
 // include/dsvg.h).  All kernels are thread-per-feature-column with coalesced row accesses; parameter
 // gradients are accumulated privately (registers / LDS columns owned by one thread) and reduced through
 // per-workgroup partial rows -> no global atomics anywhere, bit-reproducible results.
-#include "dsvg_common.h"
+#include "mfma_frag.h"
 #include "../../include/dsvg.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -423,11 +423,7 @@ __global__ __launch_bounds__(256) void embed_scatter_arg_kernel(const float* __r
 // A workgroup of 8 waves owns ES_TOK_PER_BLOCK tokens; wave w accumulates table rows 32 w .. 32 w + 31 (wave 0 also the
 // rows from 256 on), both 32-column halves: fp32 accumulation in a FIXED order - unlike the LDS float atomics of the
 // kernel above, which also run at a fraction of a lane per clock (93 us for 41 k tokens; this one is bound by reading dA).
-typedef __bf16 es_bf16x8 __attribute__((ext_vector_type(8)));
-typedef short es_shortx4 __attribute__((ext_vector_type(4)));
-typedef float es_floatx16 __attribute__((ext_vector_type(16)));
 constexpr int ESM_LD = 11 * 64 + 8;         // row stride (elements) of the staged gradient rows: 1424 B = 89 x 16 B
-__device__ __forceinline__ int es_rowmap(int r, int h2) { return (r & 3) + 8 * (r >> 2) + 4 * h2; }
 __global__ __launch_bounds__(512) void embed_scatter_arg_mfma_kernel(const float* __restrict__ args,
                                                                      const bf16_t* __restrict__ dA, float* __restrict__ part,
                                                                      long long T_tok, int n_args, int n_argvals) {
@@ -440,7 +436,7 @@ __global__ __launch_bounds__(512) void embed_scatter_arg_mfma_kernel(const float
     const long long t0 = (long long)blockIdx.x * ES_TOK_PER_BLOCK;
     const long long t1 = min(T_tok, t0 + ES_TOK_PER_BLOCK);
     const int n_vt = wave == 0 && n_argvals > 256 ? 2 : 1;             // value tiles of this wave: w (and 8 for wave 0)
-    es_floatx16 acc[2][2];
+    floatx16 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -465,13 +461,13 @@ __global__ __launch_bounds__(512) void embed_scatter_arg_mfma_kernel(const float
         __syncthreads();
         for (int a = 0; a < n_args; ++a) {
             // the one-hot B fragments of this slot: lane (table row li of the tile, half h2), K slot e of step ks = token
-            // row es_rowmap(8 ks + e, h2) - the K order of the transposed reads below
-            es_bf16x8 oh[2][2];
+            // row rowmap(8 ks + e, h2) - the K order of the transposed reads below
+            bf16x8 oh[2][2];
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 int tok_idx[8];
 #pragma unroll
-                for (int e = 0; e < 8; ++e) tok_idx[e] = sidx[es_rowmap(8 * ks + e, h2) * 16 + a];
+                for (int e = 0; e < 8; ++e) tok_idx[e] = sidx[rowmap(8 * ks + e, h2) * 16 + a];
 #pragma unroll
                 for (int vt = 0; vt < 2; ++vt) {
                     if (vt >= n_vt) break;      // (wave-uniform)
@@ -480,9 +476,9 @@ __global__ __launch_bounds__(512) void embed_scatter_arg_mfma_kernel(const float
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
                         w[e] = (tok_idx[2 * e] == v ? 0x3f80u : 0u) | (tok_idx[2 * e + 1] == v ? 0x3f800000u : 0u);
-                    union { es_bf16x8 v8; uint4 u; } f;
+                    Frag8 f;
                     f.u = make_uint4(w[0], w[1], w[2], w[3]);
-                    oh[vt][ks] = f.v8;
+                    oh[vt][ks] = f.v;
                 }
             }
 #pragma unroll
@@ -490,24 +486,24 @@ __global__ __launch_bounds__(512) void embed_scatter_arg_mfma_kernel(const float
                 const int col0 = a * 64 + 32 * ntile;
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
-                    // A[i = column col0 + (lane & 31)][K slot e] = img[row es_rowmap(8 ks + e, lane >> 5)][col0 + i]
+                    // A[i = column col0 + (lane & 31)][K slot e] = img[row rowmap(8 ks + e, lane >> 5)][col0 + i]
                     const int g = lane >> 4, q16 = lane & 15;
                     const int row = 16 * ks + 4 * (g >> 1) + (q16 >> 2);
                     const int col = col0 + 16 * (g & 1) + 4 * (q16 & 3);
-                    union { es_bf16x8 v8; es_shortx4 h[2]; } fa;
+                    Frag8 fa;
                     fa.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                        (es_shortx4 __attribute__((address_space(3)))*)(&img[row * ESM_LD + col]));
+                        (shortx4 __attribute__((address_space(3)))*)(&img[row * ESM_LD + col]));
                     fa.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                        (es_shortx4 __attribute__((address_space(3)))*)(&img[(row + 8) * ESM_LD + col]));
-                    acc[0][ntile] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa.v8, oh[0][ks], acc[0][ntile], 0, 0, 0);
+                        (shortx4 __attribute__((address_space(3)))*)(&img[(row + 8) * ESM_LD + col]));
+                    acc[0][ntile] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa.v, oh[0][ks], acc[0][ntile], 0, 0, 0);
                     if (n_vt == 2)
-                        acc[1][ntile] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa.v8, oh[1][ks], acc[1][ntile], 0, 0, 0);
+                        acc[1][ntile] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa.v, oh[1][ks], acc[1][ntile], 0, 0, 0);
                 }
             }
         }
         __syncthreads();
     }
-    // acc[vt][ntile][r] = dTable[v = tile base + li][e = 32 ntile + es_rowmap(r, h2)]
+    // acc[vt][ntile][r] = dTable[v = tile base + li][e = 32 ntile + rowmap(r, h2)]
     float* dst = part + (size_t)blockIdx.x * n_argvals * 64;
 #pragma unroll
     for (int vt = 0; vt < 2; ++vt) {
@@ -517,7 +513,7 @@ __global__ __launch_bounds__(512) void embed_scatter_arg_mfma_kernel(const float
 #pragma unroll
         for (int ntile = 0; ntile < 2; ++ntile)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) dst[(size_t)v * 64 + 32 * ntile + es_rowmap(r, h2)] = acc[vt][ntile][r];
+            for (int r = 0; r < 16; ++r) dst[(size_t)v * 64 + 32 * ntile + rowmap(r, h2)] = acc[vt][ntile][r];
     }
 }
 
@@ -842,14 +838,6 @@ __global__ void masked_mean_bwd_kernel(const T* __restrict__ dout, const uint64_
 // Round 6: the bf16 FORWARD kernel with a thread per (sequence, 8 columns): 16-byte loads instead of 2-byte ones (the one-column
 // threads above ran the 41 k-row pooling at 1.2 TB/s: 18.2 -> 9.3 us).  Every column is still summed over its rows in increasing order:
 // bit-identical.
-__device__ __forceinline__ void mm_unpack8(const uint4& t, float (&v)[8]) {
-    const uint32_t w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        v[2 * e] = __uint_as_float(w[e] << 16);
-        v[2 * e + 1] = __uint_as_float(w[e] & 0xffff0000u);
-    }
-}
 __device__ __forceinline__ bool mm_seq(const uint64_t* mask, const int32_t* seq_off, long long b, int& S, long long& row0,
                                        uint64_t& m) {
     if (seq_off) {
@@ -885,7 +873,7 @@ __global__ __launch_bounds__(256) void masked_mean_fwd8_kernel(const bf16_t* __r
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             float v[8];
-            mm_unpack8(t[k], v);
+            unpack8(t[k], v);
             if ((m >> (i + k)) & 1ull) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) s[e] += v[e];
@@ -895,7 +883,7 @@ __global__ __launch_bounds__(256) void masked_mean_fwd8_kernel(const bf16_t* __r
     for (; i < S; ++i) {
         if ((m >> i) & 1ull) {
             float v[8];
-            mm_unpack8(*reinterpret_cast<const uint4*>(px + (long long)i * d), v);
+            unpack8(*reinterpret_cast<const uint4*>(px + (long long)i * d), v);
 #pragma unroll
             for (int e = 0; e < 8; ++e) s[e] += v[e];
         }

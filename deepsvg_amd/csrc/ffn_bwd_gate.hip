@@ -20,12 +20,8 @@
 // reads and the transposed reads alike; 128-byte rows (read transposed only): ch ^ (((r >> 1) & 1) << 2).
 // Rows past the slice's end (ragged row count, clamped on the load side) are zeroed in the G2p operand and not stored.
 #include <stdlib.h>
-#include "dsvg_common.h"
+#include "mfma_frag.h"
 #include "../../include/dsvg.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short shortx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
@@ -36,14 +32,6 @@ constexpr int HP_OFF = 2 * 64 * 128 * 2;     // hp image inside a slot
 constexpr int NSLOT = 3;
 constexpr int LDS_BYTES = W2_BYTES + NSLOT * SLOT;
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget of a CU");
-
-#define DSVG_LDS_PTR(p) ((void __attribute__((address_space(3)))*)(p))
-
-union Frag8 {
-    bf16x8 v;
-    shortx4 h[2];
-    uint4 u;
-};
 
 __device__ __forceinline__ int sw256(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
 __device__ __forceinline__ int sw128(int r) { return ((r >> 1) & 1) << 2; }

@@ -1,33 +1,12 @@
-// Helpers shared by the fused token-stationary kernels (ffn_fused.hip, attn_fused.hip): packed MFMA fragment images
-// streamed through an LDS ring by LDS-DMA, bf16 <-> fp32 register packing, accumulator-tile transposition.
+// Helpers specific to the fused token-stationary kernels (ffn_fused.hip, attn_fused.hip, ...): packed MFMA fragment
+// images streamed through an LDS ring by LDS-DMA, LayerNorm statistics of packed rows, accumulator-tile transposition.
+// The operand-layout helpers every MFMA kernel shares (Frag8, rowmap, pack8 / unpack8, ...) come from mfma_frag.h.
 #pragma once
-#include "dsvg_common.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
+#include "mfma_frag.h"
 
 namespace {
 
 constexpr int FRAG = 1024;              // bytes per packed MFMA fragment (64 lanes x 16 B)
-
-#define DSVG_LDS_PTR(p) ((void __attribute__((address_space(3)))*)(p))
-
-union Frag8 {
-    bf16x8 v;
-    uint4 u;
-};
-
-__device__ __forceinline__ void unpack8(const uint4& t, float (&v)[8]) {
-    const uint32_t w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        v[2 * e] = __uint_as_float(w[e] << 16);
-        v[2 * e + 1] = __uint_as_float(w[e] & 0xffff0000u);
-    }
-}
-__device__ __forceinline__ uint4 pack8(const float (&v)[8]) {
-    return make_uint4(f2bf_pk(v[0], v[1]), f2bf_pk(v[2], v[3]), f2bf_pk(v[4], v[5]), f2bf_pk(v[6], v[7]));
-}
 
 // LayerNorm statistics of a row whose 256 bf16 values sit packed in the registers of a lane pair (16 x uint4 per lane): sum
 // and sum of squares straight from the packed words - v_dot2c_f32_bf16 with (1, 1) and with the word itself, one instruction
@@ -59,8 +38,6 @@ __device__ __forceinline__ void ln_mean_rstd256(float s, float q, float eps, flo
     mean = s * (1.f / 256.f);
     rstd = rsqrtf(fmaxf(q * (1.f / 256.f) - mean * mean, 0.f) + eps);
 }
-
-
 
 // ---------------------------------------------------------------------------------------------------------------------
 // LDS-DMA of one wave's 4 consecutive 1 KiB pieces (hidden from hipcc, see the header).  src: per-lane address of the

@@ -5,7 +5,7 @@
 // bf16 path : see gemm_bf16.hip (v_mfma_f32_32x32x16_bf16).
 // Replaces aten::addmm/mm for every nn.Linear on the path and their autograd matmuls
 // (reference call sites are listed in include/dsvg.h).
-#include "dsvg_common.h"
+#include "mfma_frag.h"
 #include "../../include/dsvg.h"
 #include "gemm_common.h"
 int dsvg_gemm_group_flush(hipStream_t st);       // gemm_bf16_glds.hip
@@ -54,7 +54,6 @@ __global__ void gemm_naive_kernel(dsvg_gemm_desc p, int k_begin, int k_end, floa
 //   operand fragments (guide §3): A: lane l holds A[i=l&31][k=l>>5], B: B[k=l>>5][j=l&31]
 //   C/D: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
 // ---------------------------------------------------------------------------------------------
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int BM = 128, BN = 128, BK = 32;
 
@@ -281,6 +280,7 @@ __global__ __launch_bounds__(256) void gemm_f32_mfma_kernel(dsvg_gemm_desc p, in
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
+                // (rowmap(r, lane >> 5) written out, here and below: a call inside this sum changes every variant's registers)
                 const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                 if (m < p.M) rs_part[(size_t)kz * dsvg_splitk_slice(p.M, p.N, true) + m] = accb[i][r];
             }

@@ -12,26 +12,11 @@
 //   uses are compile-time variants (EPI_*), so the hot kernels carry no dead branches or RNG code.
 #include "gemm_bf16.h"
 #include "gemm_common.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short shortx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
+#include "mfma_frag.h"
 
 constexpr int TBM = 128, TBN = 128, TBK = 64;
 constexpr int LDK = 72;
 constexpr int LDM = 160;
-
-__device__ __forceinline__ void unpack8(const uint4& t, float (&v)[8]) {
-    const uint32_t w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        v[2 * e] = __uint_as_float(w[e] << 16);
-        v[2 * e + 1] = __uint_as_float(w[e] & 0xffff0000u);
-    }
-}
-__device__ __forceinline__ uint4 pack8(const float (&v)[8]) {
-    return make_uint4(f2bf_pk(v[0], v[1]), f2bf_pk(v[2], v[3]), f2bf_pk(v[4], v[5]), f2bf_pk(v[6], v[7]));
-}
 
 // dropout replay on an 8-element chunk of operand A whose first element has id e
 __device__ __forceinline__ uint4 drop_chunk8(uint4 t, const DropCtx& dc, uint64_t e) {
@@ -58,12 +43,6 @@ __device__ __forceinline__ uint4 mask_tail8(uint4 v, int nvalid) {
     }
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
-
-union Frag8 {
-    bf16x8 v;
-    shortx4 h[2];
-    uint4 u;
-};
 
 template <bool AKC, bool BKC, bool ADROP, int EPI>
 __global__ __launch_bounds__(256) void gemm_bf16_mfma_kernel(dsvg_gemm_desc p, int tiles_n, int nwg_mn,
@@ -242,6 +221,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_mfma_kernel(dsvg_gemm_desc p, i
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
+                    // (rowmap(r, lane >> 5) written out, here and below: a call inside this sum changes every variant's registers)
                     const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                     const int n = n0 + wn * 64 + j * 32 + (lane & 31);
                     if (m < p.M && n < p.N) my_part[(size_t)m * p.N + n] = acc[i][j][r];
@@ -289,7 +269,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_mfma_kernel(dsvg_gemm_desc p, i
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int row = rowmap(r, lane >> 5);
             slab[row * SLD + (lane & 31)] = c0[r];
             slab[row * SLD + 32 + (lane & 31)] = c1[r];
         }

@@ -15,39 +15,15 @@
 //   * out-of-range rows are clamped on the load side (their results are never stored): no exec-mask branches.
 // Eligibility is decided on the host (dsvg_gemm_bf16_glds_try); everything else runs on gemm_bf16.hip.
 #include "gemm_bf16.h"
+#include "mfma_frag.h"
 #include <map>
 #include <mutex>
 #include <vector>
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short shortx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
 constexpr int GBM = 128, GBN = 128, GBK = 64;
 constexpr int IMG = 128 * 64;          // elements per operand image (16 KiB)
-
-#define DSVG_LDS_PTR(p) ((void __attribute__((address_space(3)))*)(p))
-#define DSVG_GLB_PTR(p) ((const void __attribute__((address_space(1)))*)(p))
-
-union Frag8 {
-    bf16x8 v;
-    shortx4 h[2];
-    uint4 u;
-};
-
-__device__ __forceinline__ void unpack8(const uint4& t, float (&v)[8]) {
-    const uint32_t w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        v[2 * e] = __uint_as_float(w[e] << 16);
-        v[2 * e + 1] = __uint_as_float(w[e] & 0xffff0000u);
-    }
-}
-__device__ __forceinline__ uint4 pack8(const float (&v)[8]) {
-    return make_uint4(f2bf_pk(v[0], v[1]), f2bf_pk(v[2], v[3]), f2bf_pk(v[4], v[5]), f2bf_pk(v[6], v[7]));
-}
 
 // One K step of both operands by LDS-DMA issued from inline asm (8 instructions per wave: 4 pieces of A, 4 of B), for the
 // 4-stage variant: hipcc drains vmcnt(0) before the first ds_read after a *builtin* LDS-DMA, which would serialise a deep

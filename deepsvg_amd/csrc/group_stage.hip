@@ -25,8 +25,6 @@
 #include "pack_images.h"
 #include "../../include/dsvg.h"
 
-typedef short shortx4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 constexpr int GD = 256;                 // d_model
@@ -38,7 +36,6 @@ constexpr int LDH = GF + 8;             // hidden image: 1040 B = 65 x 16 B
 constexpr int GS_FRAGS = 128;           // weight fragments per wave and layer (both directions)
 constexpr int GS_PF_DEFAULT = 12;       // prefetch distance of the weight stream (fragments = KiB in flight per wave)
 
-using dsvg_pack::rowmap;
 static_assert(dsvg_pack::GS_FRAGS == GS_FRAGS && dsvg_pack::D == GD && dsvg_pack::F == GF && dsvg_pack::H == GH, "pack_images.h restates these");
 
 // weight packing (dsvg_gs_pack): fp32 master parameters -> bf16 MFMA A fragments, wave-major, in consumption order; body
@@ -51,55 +48,7 @@ __global__ __launch_bounds__(256) void gs_pack_kernel(const float* __restrict__ 
 // ---------------------------------------------------------------------------------------------------------------------
 // LDS image helpers
 // ---------------------------------------------------------------------------------------------------------------------
-// B operand: B[k = 16 step + 8 h2 + e][column = row `row` of the image] - one 16-byte read
-__device__ __forceinline__ bf16x8 row_frag(const bf16_t* img, int ld, int row, int col0, int step, int h2) {
-    Frag8 f;
-    f.u = *reinterpret_cast<const uint4*>(&img[row * ld + col0 + 16 * step + 8 * h2]);
-    return f.v;
-}
-// A operand: A[i = column col0 + (lane & 31)][k slot e] = img[row rowmap(8 ks + e, lane >> 5)][that column]
-__device__ __forceinline__ bf16x8 col_frag(const bf16_t* img, int ld, int col0, int ks, int lane) {
-    const int g = lane >> 4, q16 = lane & 15;
-    const int row = 16 * ks + 4 * (g >> 1) + (q16 >> 2);
-    const int col = col0 + 16 * (g & 1) + 4 * (q16 & 3);
-    union { bf16x8 v; shortx4 h[2]; } f;
-    f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((shortx4 __attribute__((address_space(3)))*)(&img[row * ld + col]));
-    f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((shortx4 __attribute__((address_space(3)))*)(&img[(row + 8) * ld + col]));
-    return f.v;
-}
-__device__ __forceinline__ bf16x8 pack_regs(const float (&p)[16], int ks) {
-    Frag8 f;
-    f.u = make_uint4(f2bf_pk(p[8 * ks + 0], p[8 * ks + 1]), f2bf_pk(p[8 * ks + 2], p[8 * ks + 3]),
-                     f2bf_pk(p[8 * ks + 4], p[8 * ks + 5]), f2bf_pk(p[8 * ks + 6], p[8 * ks + 7]));
-    return f.v;
-}
-// a transposed 32 x 32 result tile (lane: row `row`, columns col0 + rowmap(r, h2)) -> four 8-byte pieces per lane
-__device__ __forceinline__ void stage_rows(bf16_t* img, int ld, int row, int col0, int h2, const float (&v)[16]) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        uint2 t;
-        t.x = f2bf_pk(v[4 * c + 0], v[4 * c + 1]);
-        t.y = f2bf_pk(v[4 * c + 2], v[4 * c + 3]);
-        *reinterpret_cast<uint2*>(&img[row * ld + col0 + 8 * c + 4 * h2]) = t;
-    }
-}
-// the lane's 16 values of such a tile, read back (bf16 -> fp32)
-__device__ __forceinline__ void load_rows(const bf16_t* img, int ld, int row, int col0, int h2, float (&v)[16]) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const uint2 t = *reinterpret_cast<const uint2*>(&img[row * ld + col0 + 8 * c + 4 * h2]);
-        v[4 * c + 0] = __uint_as_float(t.x << 16); v[4 * c + 1] = __uint_as_float(t.x & 0xffff0000u);
-        v[4 * c + 2] = __uint_as_float(t.y << 16); v[4 * c + 3] = __uint_as_float(t.y & 0xffff0000u);
-    }
-}
-// rows [0, S) x `cols` columns of an image -> global rows (16 bytes per lane, whole workgroup)
-__device__ __forceinline__ void store_image(bf16_t* dst, long long ld_dst, const bf16_t* img, int ld, int col0, int S, int cols) {
-    const int cpr = cols / 8;
-    for (int idx = threadIdx.x; idx < S * cpr; idx += 512) {
-        const int r = idx / cpr, c = idx % cpr;
-        *reinterpret_cast<uint4*>(dst + (long long)r * ld_dst + 8 * c) = *reinterpret_cast<const uint4*>(img + r * ld + col0 + 8 * c);
-    }
-}
+// row_frag / col_frag / pack_regs / stage_rows / load_rows / store_image: mfma_frag.h
 // hidden image [S][512] -> global rows with fragment-ordered columns (position p holds unit (p & ~12) | ((p & 4) << 1) |
 // ((p & 8) >> 1), csrc/ffn_fused.hip frag_pos): the 16-byte piece q of a row = the 8-byte granules at columns
 // 16 (q >> 1) + 4 (q & 1) and + 8

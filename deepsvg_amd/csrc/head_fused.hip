@@ -28,8 +28,6 @@ constexpr int HNBUF = 3;
 constexpr int H_MAX_COLS = 3072;        // bias staging
 enum { MODE_ARGMAX = 0, MODE_LSE = 1, MODE_DLOGITS = 2 };
 
-__host__ __device__ inline int hrowmap(int r, int h2) { return (r & 3) + 8 * (r >> 2) + 4 * h2; }
-
 // img[chunk][tile t][K step ks][lane l][e] = W[64 chunk + 32 t + (l & 31)][16 ks + 8 (l >> 5) + e], zero rows past n_out
 __global__ __launch_bounds__(256) void head_pack_kernel(const bf16_t* __restrict__ w, int n_out, int n_chunks,
                                                         bf16_t* __restrict__ img) {
@@ -206,7 +204,7 @@ __global__ __launch_bounds__(512, 1) void head_kernel(HeadArgs a) {
                 float d[16];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int col = cb + hrowmap(r, h2);
+                    const int col = cb + rowmap(r, h2);
                     const bool nx = col >= slot_hi;
                     const float w_ = nx ? wr_n : wr;
                     const float sm = __expf(v[r] - (nx ? ls_n : ls)) - (col == (nx ? tcol_n : tcol) ? 1.f : 0.f);
@@ -238,7 +236,7 @@ __global__ __launch_bounds__(512, 1) void head_kernel(HeadArgs a) {
                     if (MODE == MODE_ARGMAX) {
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
-                            const int col = cb + hrowmap(r, h2);
+                            const int col = cb + rowmap(r, h2);
                             const bool in = col >= lo && col < hi;
                             if (in && v[r] > st_m) { st_m = v[r]; st_i = col; }
                         }
@@ -246,7 +244,7 @@ __global__ __launch_bounds__(512, 1) void head_kernel(HeadArgs a) {
                         float u[16], cm = -INFINITY;
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
-                            const int col = cb + hrowmap(r, h2);
+                            const int col = cb + rowmap(r, h2);
                             u[r] = (col >= lo && col < hi) ? v[r] : -INFINITY;
                             cm = fmaxf(cm, u[r]);
                             st_t += (col == tcol && col >= lo && col < hi) ? v[r] : 0.f;

@@ -4,7 +4,7 @@
 // dsvg_cast_weights) and the one-launch refresh of a training step (dsvg_pack_images, pack_images.hip) run the same code.
 // Layouts are documented where the consumers live (ffn_fused.hip, attn_fused.hip, attention_mfma.hip, group_stage.hip).
 #pragma once
-#include "dsvg_common.h"
+#include "mfma_frag.h"
 
 namespace dsvg_pack {
 
@@ -13,12 +13,7 @@ constexpr int F = 512;                  // dim_feedforward
 constexpr int H = 8;                    // heads
 constexpr int FRAG_BYTES = 1024;        // bytes per packed MFMA fragment (64 lanes x 16 B)
 
-__device__ __forceinline__ uint4 pack8(const float (&v)[8]) {
-    return make_uint4(f2bf_pk(v[0], v[1]), f2bf_pk(v[2], v[3]), f2bf_pk(v[4], v[5]), f2bf_pk(v[6], v[7]));
-}
-
-// the register order of a transposed 32 x 32 MFMA tile: value r of lane half h2 belongs to row / column rowmap(r, h2)
-__host__ __device__ inline int rowmap(int r, int h2) { return (r & 3) + 8 * (r >> 2) + 4 * h2; }
+// rowmap(r, h2), the register order of a transposed 32 x 32 MFMA tile, and pack8 come from mfma_frag.h
 
 // ---- fused FFN (ffn_fused.hip) ---------------------------------------------------------------------------------------
 constexpr int FFN_CH = 32;              // hidden units per chunk

@@ -36,3 +36,46 @@ def test_committed_ffn_traffic_was_measured_on_this_kernel_source():
     t = json.load(open(os.path.join(ROOT, "profiles", "ffn_traffic.json")))
     assert t["ffn_fused_hip_code_sha256_16"] == bench.kernel_source_hash(os.path.join(ROOT, "deepsvg_amd", "csrc", "ffn_fused.hip"))
     assert t.get("commit")
+
+
+def _csrc_code():
+    """{file name: text} of csrc/*.hip and csrc/*.h with comments removed the way bench.kernel_source_hash removes them"""
+    d = os.path.join(ROOT, "deepsvg_amd", "csrc")
+    out = {}
+    for f in sorted(os.listdir(d)):
+        if f.endswith((".hip", ".h")):
+            t = open(os.path.join(d, f)).read()
+            t = re.sub(r"/\*.*?\*/", "", t, flags=re.S)
+            out[f] = re.sub(r"//[^\n]*", "", t)
+    return out
+
+
+def _definitions(text, name):
+    """how often `name(parameters) {` occurs: a function definition, as opposed to a call or a using-declaration"""
+    n = 0
+    for m in re.finditer(r"(?<![\w.])%s\s*\(" % name, text):
+        depth, i = 1, m.end()
+        while depth and i < len(text):
+            depth += {"(": 1, ")": -1}.get(text[i], 0)
+            i += 1
+        n += re.match(r"\s*\{", text[i:]) is not None
+    return n
+
+
+def test_mfma_operand_layout_is_stated_once():
+    """The 32 x 32 MFMA row map and the image <-> operand accessors are a contract between the host-side weight packers and
+    every kernel (csrc/mfma_frag.h): one definition of each in csrc, and the row-map formula written out once, so that a fix
+    or a layout change cannot leave a private copy behind.  Finds duplication only; scripts/isa_diff.py checks the code."""
+    code = _csrc_code()
+    where = lambda count: {f: count(t) for f, t in code.items() if count(t)}
+    for name in ("rowmap", "row_frag", "col_frag", "pack_regs", "stage_rows", "load_rows", "unpack8", "pack8"):
+        assert where(lambda t: _definitions(t, name)) == {"mfma_frag.h": 1}, name
+    assert where(lambda t: len(re.findall(r"\bunion\s+Frag8\s*\{", t))) == {"mfma_frag.h": 1}
+    # the 8 x bf16 operand vector, under whatever name
+    assert where(lambda t: len(re.findall(r"\btypedef\s+__bf16\s+\w+\s+__attribute__\s*\(\(\s*ext_vector_type\(8\)", t))) == {"mfma_frag.h": 1}
+    # (r & 3) + 8 * (r >> 2) + 4 * h2, whatever the operands are called: once, in the header.  Kept apart, by name and count:
+    # the C-tile row index of the two tiled GEMMs, where the terms are part of a longer sum `m0 + wm * 64 + i * 32 + ...` -
+    # hipcc allocates the registers of all 24 kernels differently for any spelling of that sum which calls rowmap()
+    kept = {"gemm.hip": 2, "gemm_bf16.hip": 2}
+    formula = r"\(\s*(\w+)\s*&\s*3\s*\)\s*\+\s*8\s*\*\s*\(\s*\1\s*>>\s*2\s*\)\s*\+\s*4\s*\*"
+    assert where(lambda t: len(re.findall(formula, t))) == {"mfma_frag.h": 1, **kept}
