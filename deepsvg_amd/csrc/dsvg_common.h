@@ -8,6 +8,7 @@
 
 #define DSVG_F32 0
 #define DSVG_BF16 1
+#define DSVG_I64 2
 
 typedef uint16_t bf16_t;  // raw bfloat16 bits; arithmetic is always done in fp32
 

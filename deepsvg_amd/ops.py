@@ -1202,6 +1202,45 @@ def match_assign(cost, vis):
 
 
 # ------------------------------------------------------------------------------------------------
+# reconstruction error of decoded icons (difflib/tensor.py:191-230, difflib/loss.py:5-7), evaluation only
+# ------------------------------------------------------------------------------------------------
+def sample_points(commands, args, n=10, groups=1):
+    """commands [B*groups, L] / args [B*groups, L, 11], both float32 or both int64 (read as they are) ->
+    points f32 [B, cap, 2] with cap = groups * (L * (n - 1) + 1), counts int32 [B]: n points per `l` / `c` command, the
+    shared end points once, the `groups` sequences of a cloud concatenated; rows past counts[b] are not written"""
+    _chk(commands, args)
+    assert commands.dim() == 2 and args.dim() == 3 and args.shape[:2] == commands.shape and args.shape[2] == 11
+    assert commands.dtype == args.dtype and commands.dtype in (torch.float32, torch.int64)
+    assert commands.is_contiguous() and args.is_contiguous()
+    assert groups >= 1 and commands.shape[0] % groups == 0
+    B, L = commands.shape[0] // groups, commands.shape[1]
+    points = torch.empty(B, groups * (L * (n - 1) + 1), 2, dtype=torch.float32, device=commands.device)
+    counts = torch.empty(B, dtype=torch.int32, device=commands.device)
+    _l.check(_l.load().dsvg_sample_points(F32 if commands.dtype == torch.float32 else _l.DSVG_I64, commands.data_ptr(),
+                                          args.data_ptr(), B, groups, L, int(n), points.data_ptr(), counts.data_ptr(),
+                                          _stream()), "dsvg_sample_points")
+    return points, counts
+
+
+def chamfer(px, nx, py, ny):
+    """px f32 [B, capx, 2] with nx int32 [B] points in use, py f32 [B, capy, 2] with ny int32 [B] -> f32 [B]:
+    mean_i min_j |x_i - y_j| + mean_j min_i |x_i - y_j|, NaN where a cloud is empty; no distance matrix is built"""
+    _chk(px, nx, py, ny)
+    for p, c in ((px, nx), (py, ny)):
+        assert p.dtype == torch.float32 and p.dim() == 3 and p.shape[2] == 2 and p.is_contiguous()
+        assert c.dtype == torch.int32 and c.shape == (p.shape[0],) and c.is_contiguous()
+    assert px.shape[0] == py.shape[0]
+    L = _l.load()
+    B, capx, capy = px.shape[0], px.shape[1], py.shape[1]
+    out = torch.empty(B, dtype=torch.float32, device=px.device)
+    ws_bytes = L.dsvg_chamfer_workspace_bytes(B, capx, capy)          # one partial sum per (icon, direction, 1,024 points)
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=px.device)
+    _l.check(L.dsvg_chamfer(px.data_ptr(), nx.data_ptr(), capx, py.data_ptr(), ny.data_ptr(), capy, B, out.data_ptr(),
+                            ws.data_ptr(), ws_bytes, _stream()), "dsvg_chamfer")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # device-side batch assembly (svgtensor_dataset.py:164-205)
 # ------------------------------------------------------------------------------------------------
 def assemble_batch(rows, slot_off, variant, G, L, grouped, want_args=True, want_rel=False, pad_val=-1.0,

@@ -27,6 +27,7 @@ extern "C" {
 
 #define DSVG_F32 0
 #define DSVG_BF16 1
+#define DSVG_I64 2 /* an input dtype of dsvg_sample_points only */
 
 /* ABI version: bumped on EVERY change of an exported signature (round 4: 2 - dsvg_ffn_bwd_one and
  * dsvg_attn_block_fwd_stages removed, round 3's signature changes of dsvg_defer_scope / dsvg_gather_groups /
@@ -42,8 +43,9 @@ extern "C" {
  * 10: dsvg_ffn_gate_dw2 added (the gated dpre GEMM and the dW2 split-K GEMM of the fused FFN backward as one launch).
  * 11: two-stage configs with paths of 65..256 tokens: dsvg_build_masks_lens, dsvg_pack_tokens_lens, dsvg_packed_mean_fwd /
  *     bwd, dsvg_attention_long_packed_fwd / bwd, dsvg_attention_long_mfma_fwd / bwd added.
- * 12: dsvg_ffn_bwd removed (the fully fused FFN backward: no caller since round 2; dsvg_ffn_bwd_dx is the FFN backward's kernel). */
-#define DSVG_ABI_VERSION 12
+ * 12: dsvg_ffn_bwd removed (the fully fused FFN backward: no caller since round 2; dsvg_ffn_bwd_dx is the FFN backward's kernel).
+ * 13: dsvg_sample_points / dsvg_chamfer (+ dsvg_chamfer_workspace_bytes) added (reconstruction error of decoded icons, evaluation only); DSVG_I64. */
+#define DSVG_ABI_VERSION 13
 
 const char* dsvg_last_error(void);
 int dsvg_version(void);
@@ -496,6 +498,31 @@ int dsvg_argmax_rows(int32_t dtype, const void* logits, int64_t ld, int32_t grou
  * class c is that of element (r / group, (r % group) * C + c), shared with dsvg_head_sample. */
 int dsvg_sample_rows(int32_t dtype, const void* logits, int64_t ld, int32_t group, int64_t rows, int32_t C,
                      float temperature, const void* seed, uint32_t site, int32_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Reconstruction error of decoded icons (csrc/metrics.hip), evaluation only: no gradients.
+ *  sample_points: SVGTensor.sample_points (deepsvg/difflib/tensor.py:191-230), batched.  commands [B*G, L] and args
+ *    [B*G, L, 11], both contiguous and both of dtype `itype` (DSVG_F32 as the dataset delivers them, DSVG_I64 as
+ *    greedy_sample returns them; read as they are).  The G sequences of cloud b are concatenated in group order.  Per
+ *    sequence: the start point of row i is the end position (args 9:11) of row i - 1 whatever it holds (PAD -1 included),
+ *    (0, 0) on row 0 (tensor.py:75-82); `l` (1) gives p0 + z (p3 - p0) and `c` (2) the cubic Bezier of start, control1
+ *    (5:7), control2 (7:9), end (9:11) at z_k = k / (n - 1); every such command contributes z_0 .. z_{n-2}, the last one of
+ *    the sequence z_{n-1} too (:226-228): k (n - 1) + 1 points for k drawing commands, and - where the reference raises -
+ *    0 points for k = 0.  m, a, z, SOS, EOS give nothing (:198-217).  2 <= n <= 64, G * L <= 2048.
+ *    points fp32 [B, cap, 2] with cap = G * (L * (n - 1) + 1) (< 2^31); counts int32 [B]; entries past counts[b] are
+ *    not written.
+ *  chamfer: chamfer_loss (deepsvg/difflib/loss.py:5-7) without the torch.cdist matrix, batched over clouds of different
+ *    sizes: out[b] = mean_i min_j |x_i - y_j| + mean_j min_i |x_i - y_j| (Euclidean) over the first nx[b] points of
+ *    px [B, capx, 2] and the first ny[b] of py [B, capy, 2]; NaN where either count is 0 (torch's mean of nothing).
+ *    One workgroup per (icon, direction, slice of 1,024 points) writes its sum to `workspace`
+ *    (dsvg_chamfer_workspace_bytes(B, capx, capy): 16 bytes per icon and slice of the larger cap, 8-byte aligned), a
+ *    second launch adds the slices in ascending order.  No atomics: bit-reproducible, chamfer(x, y) == chamfer(y, x) bit
+ *    for bit, chamfer(x, x) == 0. */
+int dsvg_sample_points(int32_t itype, const void* commands, const void* args, int64_t B, int32_t G, int32_t L, int32_t n,
+                       float* points, int32_t* counts, void* stream);
+int64_t dsvg_chamfer_workspace_bytes(int64_t B, int64_t capx, int64_t capy);
+int dsvg_chamfer(const float* px, const int32_t* nx, int64_t capx, const float* py, const int32_t* ny, int64_t capy,
+                 int64_t B, float* out, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The argument head fused with its consumers (csrc/head_fused.hip): args_fcn = Linear(256 -> n_args *

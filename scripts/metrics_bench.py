@@ -1,0 +1,103 @@
+"""Micro-timing of the reconstruction-error kernels (csrc/metrics.hip) at batch 512, hierarchical_ordered shapes (G = 8 groups
+of S + 2 = 32 tokens), n = 10 points per command:
+
+  ops.sample_points   float32 targets (as the dataset delivers them) and int64 sequences (as greedy_sample returns them)
+  ops.chamfer         the clouds of two different seeded batches against each other: `typical` = make_batch (1..8 visible
+                      groups, 2..30 commands each), `dense` = every group visible, `full` = every group 30 curves (2,168
+                      points in every cloud: the most these shapes give, and equal work in every workgroup)
+  the reference's way on the same GPU: a loop over icons of torch.cdist -> min -> mean (deepsvg/difflib/loss.py:5-7 restated)
+                      over the kernel's points
+
+HIP events around `inner` back-to-back calls, median of 20 such runs after warm-up.  The VALU floor quoted for the Chamfer
+launch is pairs * 4.5 vector instructions (2 subtractions, multiply, fused multiply-add, half a 3-way minimum: the kernel's inner
+loop) over 256 CUs * 4 SIMDs * 32 lanes per clock at 2.4 GHz.  Writes nothing but stdout."""
+import os
+import socket
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from deepsvg_amd import ops                          # noqa: E402
+from deepsvg_amd.synthetic import make_batch         # noqa: E402
+
+N, G, S, NPTS = 512, 8, 30, 10
+RUNS, WARMUP = 20, 5
+VALU_LANES_PER_S = 256 * 4 * 32 * 2.4e9
+
+
+def timed(fn, inner, runs=RUNS, warmup=WARMUP):
+    """-> (median, min, max) ms per call"""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(runs):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(inner):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1) / inner)
+    return statistics.median(ms), min(ms), max(ms)
+
+
+def chamfer_torch_loop(px, nx, py, ny):
+    """the reference's way, one icon at a time (counts on the host)"""
+    out = []
+    for b in range(px.shape[0]):
+        d = torch.cdist(px[b, :nx[b]], py[b, :ny[b]])
+        out.append(d.min(dim=0).values.mean() + d.min(dim=1).values.mean())
+    return torch.stack(out)
+
+
+def full_batch(seed):
+    """every group: SOS, 30 curves, EOS"""
+    commands = torch.full((N, G, S + 2), 2.0)
+    commands[:, :, 0], commands[:, :, -1] = 5.0, 4.0
+    args = torch.randint(0, 256, (N, G, S + 2, 11), generator=torch.Generator().manual_seed(seed)).float()
+    return commands.cuda(), args.cuda()
+
+
+def main():
+    assert torch.cuda.is_available(), "metrics_bench.py measures on a GPU"
+    dev = "cuda"
+    print(f"box {socket.gethostname()}: {torch.cuda.get_device_name(0)}, torch {torch.__version__}, hip {torch.version.hip}")
+    print(f"batch {N}, G = {G}, S + 2 = {S + 2}, n = {NPTS}; median [min .. max] of {RUNS} runs")
+    for tag, min_groups in (("typical", 1), ("dense", G), ("full", None)):
+        if min_groups is None:
+            (ca, aa), (cb, ab) = full_batch(1), full_batch(2)
+        else:
+            ca, aa = make_batch(N, G=G, S=S, seed=1, device=dev, min_groups=min_groups)
+            cb, ab = make_batch(N, G=G, S=S, seed=2, device=dev, min_groups=min_groups)
+        flat = lambda c, a: (c.reshape(N * G, S + 2).contiguous(), a.reshape(N * G, S + 2, 11).contiguous())     # noqa: E731
+        (c32, a32), (c64, a64) = flat(ca, aa), flat(cb.long(), ab.long())
+        in32 = c32.numel() * 4 * 12
+        px, nx = ops.sample_points(c32, a32, n=NPTS, groups=G)
+        py, ny = ops.sample_points(c64, a64, n=NPTS, groups=G)
+        out_b = int(nx.sum()) * 8
+        for name, c, a, inb in (("float32", c32, a32, in32), ("int64", c64, a64, 2 * in32)):
+            med, lo, hi = timed(lambda: ops.sample_points(c, a, n=NPTS, groups=G), inner=20)
+            print(f"[{tag}] sample_points {name}: {med * 1e3:8.1f} us [{lo * 1e3:.1f} .. {hi * 1e3:.1f}]  reads {inb / 1e6:.1f} MB, "
+                  f"writes ~{out_b / 1e6:.1f} MB of points into a {px.numel() * 4 / 1e6:.1f} MB buffer "
+                  f"({(inb + out_b) / med / 1e6:.0f} GB/s)")
+        pairs = 2 * int((nx.long() * ny.long()).sum())
+        floor_ms = pairs * 4.5 / VALU_LANES_PER_S * 1e3
+        med, lo, hi = timed(lambda: ops.chamfer(px, nx, py, ny), inner=10)
+        print(f"[{tag}] chamfer: {med * 1e3:8.1f} us [{lo * 1e3:.1f} .. {hi * 1e3:.1f}]  points per cloud mean {float(nx.float().mean()):.0f} / "
+              f"max {int(nx.max())}, {pairs / 1e9:.2f} G point pairs (both directions), {pairs / med / 1e9:.1f} T pairs/s; "
+              f"VALU floor {floor_ms * 1e3:.1f} us = {floor_ms / med * 100:.0f} % of the launch")
+        got = ops.chamfer(px, nx, py, ny)
+        nxl, nyl = nx.tolist(), ny.tolist()
+        want = chamfer_torch_loop(px, nxl, py, nyl)
+        med_t, lo_t, hi_t = timed(lambda: chamfer_torch_loop(px, nxl, py, nyl), inner=1, runs=5, warmup=1)
+        print(f"[{tag}] torch.cdist loop over {N} icons (5 runs): {med_t:8.2f} ms [{lo_t:.2f} .. {hi_t:.2f}] = {med_t / med:.0f} x the "
+              f"kernel; largest matrix {max(a * b for a, b in zip(nxl, nyl)) * 4 / 1e6:.1f} MB, all {N} at once would be "
+              f"{sum(a * b for a, b in zip(nxl, nyl)) * 4 / 1e9:.2f} GB; max |kernel - fp32 cdist| {float((got - want).abs().max()):.2e}")
+        print(f"[{tag}] mean Chamfer distance of the two batches {float(got.mean()):.4f}")
+
+
+if __name__ == "__main__":
+    main()
