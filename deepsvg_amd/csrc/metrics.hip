@@ -1,6 +1,6 @@
-// Reconstruction error of decoded icons, for evaluation only (no gradients): points sampled on the curves of a command
-// sequence (SVGTensor.sample_points, deepsvg/difflib/tensor.py:191-230) and the Chamfer distance between two such clouds
-// (chamfer_loss, deepsvg/difflib/loss.py:5-7).
+// Reconstruction error of decoded icons and its gradient: points sampled on the curves of a command sequence
+// (SVGTensor.sample_points, deepsvg/difflib/tensor.py:191-230) and the Chamfer distance between two such clouds
+// (chamfer_loss, deepsvg/difflib/loss.py:5-7), forward and backward.
 //
 // The reference samples one path at a time on the host and takes the Chamfer distance from the full torch.cdist matrix
 // (512 icons of ~2,400 points: 11.8 GB of fp32 distances).  Here:
@@ -12,6 +12,15 @@
 //                       address: a broadcast), running minimum of the SQUARED distance, one sqrt per point after the
 //                       sweep; a one-thread-per-icon finish launch adds the slices in a fixed order.  No distance matrix,
 //                       no atomics.
+//   dsvg_chamfer_nn     the same sweep in a second kernel that also keeps the arg-min index (strict <: the lowest index
+//                       wins a tie); same minima, same sums, same finish launch, so `out` has dsvg_chamfer's bits.
+//   dsvg_chamfer_bwd    the same decomposition: a thread keeps up to 4 points of its cloud and their direct terms
+//                       u(x_i, y_j*(i)) / n_x in registers; the other cloud streams through LDS as (c_j, i*(j)) with
+//                       c_j = u(x_i*(j), y_j) / n_y computed once by the loading thread; every thread adds the c_j whose index
+//                       is one of its points, in ascending j.  No atomics, no workspace, no [n_x, n_y] buffer.
+//   dsvg_sample_points_bwd  one workgroup per cloud, one thread per token: sample_points is linear in the arguments, so
+//                       a token gathers the weighted sums of its own samples' gradients (columns 5..10) and the start-point
+//                       share of the row after it (columns 9, 10), in float64, and writes all 11 columns of its row.
 #include "dsvg_common.h"
 #include "../../include/dsvg.h"
 
@@ -113,6 +122,73 @@ __global__ __launch_bounds__(SP_THREADS) void sample_points_kernel(const T* __re
     }
 }
 
+// Backward of sample_points_kernel<float>: dargs[b, t, :] from dpoints[b, :, :].  The offsets are the forward's; a token
+// reads the gradients of its own samples (weights of control1, control2, end) and those of the row after it (weight of
+// the start point, which is this row's end position whatever this row holds; row 0's start is the constant (0, 0)).
+// Weights and sums in float64: the result is the float32 nearest to the exact sum (fp32 sums of up to 2 n products of
+// weights <= 1 could pass n * 2^-22 * max|dP| only on average, not in the worst case).  Every element of the row is written.
+// A thread runs two serial loops of up to n 8-byte loads.
+__global__ __launch_bounds__(SP_THREADS) void sample_points_bwd_kernel(const float* __restrict__ commands, int G, int L, int n,
+                                                                       long long cap, const float* __restrict__ dpoints,
+                                                                       float* __restrict__ dargs) {
+    __shared__ int pre[SP_MAX_TOK + 1];
+    __shared__ int full[SP_MAX_TOK + 1];
+    __shared__ int wtot[SP_MAX_TOK / 64];
+    const long long b = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int T_ = G * L;
+    const float* cmd = commands + b * T_;
+    block_flag_scan(T_, pre, wtot, [&](int t) {
+        if (t >= T_) return false;
+        const int c = (int)cmd[t];
+        return c == SP_CMD_L || c == SP_CMD_C;
+    });
+    block_flag_scan(G, full, wtot, [&](int g) { return g < G && pre[(g + 1) * L] > pre[g * L]; });
+    const float2* dp = reinterpret_cast<const float2*>(dpoints) + b * cap;
+    float* out = dargs + b * T_ * SP_N_ARGS;
+    const double step = 1.0 / (double)(n - 1);
+    for (int t = tid; t < T_; t += SP_THREADS) {
+        const int g = t / L, i = t - g * L;
+        const int n_draw = pre[(g + 1) * L];              // drawing commands up to the end of this sequence
+        double c1x = 0.0, c1y = 0.0, c2x = 0.0, c2y = 0.0, ex = 0.0, ey = 0.0;
+        const int c = (int)cmd[t];
+        if (c == SP_CMD_L || c == SP_CMD_C) {
+            const long long o = (long long)pre[t] * (n - 1) + full[g];
+            const int cnt = pre[t] + 1 == n_draw ? n : n - 1;
+            for (int k = 0; k < cnt; ++k) {
+                const float2 d = dp[o + k];
+                const double z = (double)k * step, w = 1.0 - z;
+                if (c == SP_CMD_C) {
+                    const double w1 = 3.0 * w * w * z, w2 = 3.0 * w * z * z, w3 = z * z * z;
+                    c1x += w1 * (double)d.x; c1y += w1 * (double)d.y;
+                    c2x += w2 * (double)d.x; c2y += w2 * (double)d.y;
+                    ex += w3 * (double)d.x; ey += w3 * (double)d.y;
+                } else {
+                    ex += z * (double)d.x; ey += z * (double)d.y;
+                }
+            }
+        }
+        if (i + 1 < L) {
+            const int c_next = (int)cmd[t + 1];
+            if (c_next == SP_CMD_L || c_next == SP_CMD_C) {
+                const long long o = (long long)pre[t + 1] * (n - 1) + full[g];
+                const int cnt = pre[t + 1] + 1 == n_draw ? n : n - 1;
+                for (int k = 0; k < cnt; ++k) {
+                    const float2 d = dp[o + k];
+                    const double w = 1.0 - (double)k * step;
+                    const double w0 = c_next == SP_CMD_C ? w * w * w : w;
+                    ex += w0 * (double)d.x; ey += w0 * (double)d.y;
+                }
+            }
+        }
+        float* row = out + (long long)t * SP_N_ARGS;
+#pragma unroll
+        for (int q = 0; q < 5; ++q) row[q] = 0.f;
+        row[5] = (float)c1x; row[6] = (float)c1y; row[7] = (float)c2x; row[8] = (float)c2y;
+        row[9] = (float)ex; row[10] = (float)ey;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int CH_THREADS = 256;
 constexpr int CH_WAVES = CH_THREADS / 64;
@@ -150,6 +226,9 @@ __device__ __forceinline__ int chamfer_count(const int32_t* n, long long b, long
 // numbers).  The 16 chunks of 64 points of a slice are dealt round-robin to the 4 waves, up to CH_R chunks per wave in
 // registers; y streams through the LDS tile.  part[(b * 2 + d) * n_slices + s] takes the sum; slices past the cloud's end
 // and icons with an empty cloud write nothing (the finish kernel does not read them).
+// chamfer_nn_slice_kernel below is this kernel plus the arg-min index and must write the same `part`: a change to the
+// chunk dealing, the tile padding, the distance expression or the order of the sums is made in both (a template parameter
+// would rename this kernel and move its registers; tests/test_metrics_grad_gpu.py compares the two outputs in bits).
 __global__ __launch_bounds__(CH_THREADS) void chamfer_slice_kernel(const float* __restrict__ px, const int32_t* __restrict__ nx,
                                                                    long long capx, const float* __restrict__ py,
                                                                    const int32_t* __restrict__ ny, long long capy,
@@ -236,6 +315,200 @@ __global__ __launch_bounds__(256) void chamfer_finish_kernel(const double* __res
     out[b] = mean[0] + mean[1];
 }
 
+// chamfer_sweep with the arg-min: a[r] = the index (j0 + position in the tile) of the first point that reached m[r].  The
+// copies of the last point that pad a tile can never win: strict <.
+template <int R>
+__device__ __forceinline__ void chamfer_sweep_nn(const float4* __restrict__ tile, int cnt4, int j0, const float2 (&x)[CH_R],
+                                                 float (&m)[CH_R], int (&a)[CH_R]) {
+#pragma unroll 2
+    for (int jj = 0; jj < cnt4 / 2; jj += 2) {
+        const float4 q0 = tile[jj], q1 = tile[jj + 1];
+        const int j = j0 + 2 * jj;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            float dx = x[r].x - q0.x, dy = x[r].y - q0.y;
+            float d = fmaf(dx, dx, dy * dy);
+            if (d < m[r]) { m[r] = d; a[r] = j; }
+            dx = x[r].x - q0.z; dy = x[r].y - q0.w;
+            d = fmaf(dx, dx, dy * dy);
+            if (d < m[r]) { m[r] = d; a[r] = j + 1; }
+            dx = x[r].x - q1.x; dy = x[r].y - q1.y;
+            d = fmaf(dx, dx, dy * dy);
+            if (d < m[r]) { m[r] = d; a[r] = j + 2; }
+            dx = x[r].x - q1.z; dy = x[r].y - q1.w;
+            d = fmaf(dx, dx, dy * dy);
+            if (d < m[r]) { m[r] = d; a[r] = j + 3; }
+        }
+    }
+}
+
+// chamfer_slice_kernel, and idx_x[b, i] = arg-min_j |x_i - y_j| (d = 0) / idx_y[b, j] = arg-min_i |x_i - y_j| (d = 1) for the
+// points in use.  A kernel of its own: the forward-only launch keeps its code.  The partial sums are the same numbers.
+__global__ __launch_bounds__(CH_THREADS) void chamfer_nn_slice_kernel(const float* __restrict__ px, const int32_t* __restrict__ nx,
+                                                                      long long capx, const float* __restrict__ py,
+                                                                      const int32_t* __restrict__ ny, long long capy,
+                                                                      int n_slices, double* __restrict__ part,
+                                                                      int32_t* __restrict__ idx_x, int32_t* __restrict__ idx_y) {
+    __shared__ __attribute__((aligned(16))) float2 tile[CH_TILE];
+    __shared__ double red[CH_WAVES];
+    const long long blk = blockIdx.x;
+    const int s = (int)(blk % n_slices);
+    const long long bd = blk / n_slices, b = bd >> 1;
+    const bool swap = bd & 1;
+    const int cx = chamfer_count(nx, b, capx), cy = chamfer_count(ny, b, capy);
+    const int n_x = swap ? cy : cx, n_y = swap ? cx : cy;
+    if (n_x == 0 || n_y == 0 || (long long)s * CH_SLICE >= n_x) return;      // (block-uniform)
+    const float2* x = reinterpret_cast<const float2*>(swap ? py : px) + b * (swap ? capy : capx);
+    const float2* y = reinterpret_cast<const float2*>(swap ? px : py) + b * (swap ? capx : capy);
+    int32_t* idx = (swap ? idx_y : idx_x) + b * (swap ? capy : capx);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n_chunks = (n_x + 63) >> 6;
+
+    float2 xr[CH_R];
+    float m[CH_R];
+    int am[CH_R];
+    int nr = 0;
+#pragma unroll
+    for (int r = 0; r < CH_R; ++r) {
+        const int c = s * (CH_SLICE / 64) + r * CH_WAVES + wave;
+        if (c < n_chunks) nr = r + 1;
+        xr[r] = x[min(c * 64 + lane, n_x - 1)];
+        m[r] = INFINITY;
+        am[r] = 0;
+    }
+    for (int j0 = 0; j0 < n_y; j0 += CH_TILE) {
+        if (j0) __syncthreads();
+#pragma unroll
+        for (int h = 0; h < CH_TILE / CH_THREADS; ++h)
+            tile[h * CH_THREADS + tid] = y[min(j0 + h * CH_THREADS + tid, n_y - 1)];
+        __syncthreads();
+        const int cnt4 = (min(CH_TILE, n_y - j0) + 3) & ~3;
+        const float4* t4 = reinterpret_cast<const float4*>(tile);
+        switch (nr) {
+            case 4: chamfer_sweep_nn<4>(t4, cnt4, j0, xr, m, am); break;
+            case 3: chamfer_sweep_nn<3>(t4, cnt4, j0, xr, m, am); break;
+            case 2: chamfer_sweep_nn<2>(t4, cnt4, j0, xr, m, am); break;
+            case 1: chamfer_sweep_nn<1>(t4, cnt4, j0, xr, m, am); break;
+            default: break;
+        }
+    }
+    float sum = 0.f;
+#pragma unroll
+    for (int r = 0; r < CH_R; ++r) {
+        const int c = s * (CH_SLICE / 64) + r * CH_WAVES + wave;
+        if (c < n_chunks && c * 64 + lane < n_x) {
+            sum += sqrtf(m[r]);
+            idx[c * 64 + lane] = am[r];
+        }
+    }
+    double t = (double)sum;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+    if (lane == 0) red[wave] = t;
+    __syncthreads();
+    if (tid == 0) {
+        double tot = 0.0;
+#pragma unroll
+        for (int w = 0; w < CH_WAVES; ++w) tot += red[w];
+        part[blk] = tot;
+    }
+}
+
+// (a - b) / (|a - b| cnt); 0 where a == b (and where a coordinate is NaN)
+__device__ __forceinline__ float2 chamfer_unit_over(float2 a, float2 b, float cnt) {
+    const float dx = a.x - b.x, dy = a.y - b.y;
+    const float d2 = fmaf(dx, dx, dy * dy);
+    if (!(d2 > 0.f)) return make_float2(0.f, 0.f);
+    const float den = sqrtf(d2) * cnt;
+    return make_float2(dx / den, dy / den);
+}
+
+constexpr int CB_R = CH_SLICE / CH_THREADS;       // points of its cloud a thread owns: rows s * 1,024 + r * 256 + tid
+
+// Workgroup (icon b, direction d, slice s) writes rows s * 1,024 .. + 1,023 of dpx[b] (d = 0) or of dpy[b] (d = 1: the same
+// code on swapped pointers, so d chamfer(x, y) / dx and the second gradient of chamfer(y, x) are the same numbers):
+//   d out / d x_i = u(x_i, y_j*(i)) / n_x + sum over {j : i*(j) = i} of u(x_i, y_j) / n_y,   times dout[b]
+// with j* = ix, i* = iy the arg-min indices of the forward (clamped into their cloud here: a bad index cannot leave it).
+// Rows past the count are zero; so is every row of an icon with an empty cloud, whatever dout[b] holds.
+__global__ __launch_bounds__(CH_THREADS) void chamfer_bwd_kernel(const float* __restrict__ px, const int32_t* __restrict__ nx,
+                                                                 long long capx, const float* __restrict__ py,
+                                                                 const int32_t* __restrict__ ny, long long capy,
+                                                                 const int32_t* __restrict__ idx_x,
+                                                                 const int32_t* __restrict__ idx_y, const float* __restrict__ dout,
+                                                                 int n_slices, float* __restrict__ dpx, float* __restrict__ dpy) {
+    __shared__ __attribute__((aligned(16))) float4 tile[CH_TILE];      // (c_j.x, c_j.y, i*(j), -)
+    const long long blk = blockIdx.x;
+    const int s = (int)(blk % n_slices);
+    const long long bd = blk / n_slices, b = bd >> 1;
+    const bool swap = bd & 1;
+    const long long cap_x = swap ? capy : capx, cap_y = swap ? capx : capy;
+    const long long row0 = (long long)s * CH_SLICE;
+    if (row0 >= cap_x) return;                                         // (block-uniform)
+    const int tid = threadIdx.x;
+    const int cx = chamfer_count(nx, b, capx), cy = chamfer_count(ny, b, capy);
+    const int n_x = swap ? cy : cx, n_y = swap ? cx : cy;
+    float2* g = reinterpret_cast<float2*>(swap ? dpy : dpx) + b * cap_x;
+    if (n_x == 0 || n_y == 0 || row0 >= n_x) {                         // nothing in use in these rows (block-uniform)
+#pragma unroll
+        for (int r = 0; r < CB_R; ++r) {
+            const long long i = row0 + r * CH_THREADS + tid;
+            if (i < cap_x) g[i] = make_float2(0.f, 0.f);
+        }
+        return;
+    }
+    const float2* x = reinterpret_cast<const float2*>(swap ? py : px) + b * cap_x;
+    const float2* y = reinterpret_cast<const float2*>(swap ? px : py) + b * cap_y;
+    const int32_t* ix = (swap ? idx_y : idx_x) + b * cap_x;
+    const int32_t* iy = (swap ? idx_x : idx_y) + b * cap_y;
+    const float fx = (float)n_x, fy = (float)n_y;
+
+    float2 acc[CB_R];
+    int mine[CB_R];
+#pragma unroll
+    for (int r = 0; r < CB_R; ++r) {
+        const int i = (int)row0 + r * CH_THREADS + tid;
+        acc[r] = make_float2(0.f, 0.f);
+        mine[r] = -1;
+        if (i < n_x) {
+            const int j = min(max(ix[i], 0), n_y - 1);
+            acc[r] = chamfer_unit_over(x[i], y[j], fx);
+            mine[r] = i;
+        }
+    }
+    for (int j0 = 0; j0 < n_y; j0 += CH_TILE) {
+        if (j0) __syncthreads();
+#pragma unroll
+        for (int h = 0; h < CH_TILE / CH_THREADS; ++h) {
+            const int jl = h * CH_THREADS + tid, j = j0 + jl;
+            float4 e = make_float4(0.f, 0.f, __int_as_float(-2), 0.f);
+            if (j < n_y) {
+                const int i = min(max(iy[j], 0), n_x - 1);
+                const float2 c = chamfer_unit_over(x[i], y[j], fy);
+                e = make_float4(c.x, c.y, __int_as_float(i), 0.f);
+            }
+            tile[jl] = e;
+        }
+        __syncthreads();
+        const int cnt = min(CH_TILE, n_y - j0);
+        for (int jl = 0; jl < cnt; ++jl) {
+            const float4 e = tile[jl];                    // the same address in every lane
+            const int i = __float_as_int(e.z);
+#pragma unroll
+            for (int r = 0; r < CB_R; ++r) {
+                const bool hit = i == mine[r];
+                acc[r].x += hit ? e.x : 0.f;
+                acc[r].y += hit ? e.y : 0.f;
+            }
+        }
+    }
+    const float d = dout[b];
+#pragma unroll
+    for (int r = 0; r < CB_R; ++r) {
+        const long long i = row0 + r * CH_THREADS + tid;
+        if (i < cap_x) g[i] = mine[r] >= 0 ? make_float2(d * acc[r].x, d * acc[r].y) : make_float2(0.f, 0.f);
+    }
+}
+
 inline int64_t chamfer_slices(int64_t capx, int64_t capy) {
     return ((capx > capy ? capx : capy) + CH_SLICE - 1) / CH_SLICE;
 }
@@ -285,5 +558,59 @@ extern "C" int dsvg_chamfer(const float* px, const int32_t* nx, int64_t capx, co
     hipLaunchKernelGGL(chamfer_finish_kernel, dim3((unsigned)dsvg_cdiv(B, 256)), dim3(256), 0, st, (const double*)workspace,
                        nx, (long long)capx, ny, (long long)capy, (int)n_slices, (long long)B, out);
     DSVG_LAUNCH_CHECK("chamfer_finish");
+    return 0;
+}
+
+extern "C" int dsvg_chamfer_nn(const float* px, const int32_t* nx, int64_t capx, const float* py, const int32_t* ny,
+                               int64_t capy, int64_t B, float* out, int32_t* idx_x, int32_t* idx_y, void* workspace,
+                               int64_t workspace_bytes, void* stream) {
+    DSVG_CHECK_ARG(px && nx && py && ny && out && idx_x && idx_y && workspace, "chamfer_nn: null pointer");
+    DSVG_CHECK_ARG(B > 0 && B < (1ll << 31) && capx > 0 && capy > 0 && capx < (1ll << 31) && capy < (1ll << 31),
+                   "chamfer_nn: bad shape (B=%lld capx=%lld capy=%lld; clouds hold 1 .. 2^31 - 1 points)", (long long)B,
+                   (long long)capx, (long long)capy);
+    const int64_t n_slices = chamfer_slices(capx, capy), blocks = B * 2 * n_slices;
+    DSVG_CHECK_ARG(blocks < (1ll << 31), "chamfer_nn: %lld workgroups (B=%lld, %lld slices of %d points, 2 directions)",
+                   (long long)blocks, (long long)B, (long long)n_slices, CH_SLICE);
+    DSVG_CHECK_ARG(workspace_bytes >= dsvg_chamfer_workspace_bytes(B, capx, capy) && ((uintptr_t)workspace & 7) == 0,
+                   "chamfer_nn: workspace of %lld bytes, need %lld (8-byte aligned)", (long long)workspace_bytes,
+                   (long long)dsvg_chamfer_workspace_bytes(B, capx, capy));
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(chamfer_nn_slice_kernel, dim3((unsigned)blocks), dim3(CH_THREADS), 0, st, px, nx, (long long)capx, py,
+                       ny, (long long)capy, (int)n_slices, (double*)workspace, idx_x, idx_y);
+    DSVG_LAUNCH_CHECK("chamfer_nn");
+    hipLaunchKernelGGL(chamfer_finish_kernel, dim3((unsigned)dsvg_cdiv(B, 256)), dim3(256), 0, st, (const double*)workspace,
+                       nx, (long long)capx, ny, (long long)capy, (int)n_slices, (long long)B, out);
+    DSVG_LAUNCH_CHECK("chamfer_finish");
+    return 0;
+}
+
+extern "C" int dsvg_chamfer_bwd(const float* px, const int32_t* nx, int64_t capx, const float* py, const int32_t* ny,
+                                int64_t capy, int64_t B, const int32_t* idx_x, const int32_t* idx_y, const float* dout,
+                                float* dpx, float* dpy, void* stream) {
+    DSVG_CHECK_ARG(px && nx && py && ny && idx_x && idx_y && dout && dpx && dpy, "chamfer_bwd: null pointer");
+    DSVG_CHECK_ARG(B > 0 && B < (1ll << 31) && capx > 0 && capy > 0 && capx < (1ll << 31) && capy < (1ll << 31),
+                   "chamfer_bwd: bad shape (B=%lld capx=%lld capy=%lld; clouds hold 1 .. 2^31 - 1 points)", (long long)B,
+                   (long long)capx, (long long)capy);
+    const int64_t n_slices = chamfer_slices(capx, capy), blocks = B * 2 * n_slices;
+    DSVG_CHECK_ARG(blocks < (1ll << 31), "chamfer_bwd: %lld workgroups (B=%lld, %lld slices of %d points, 2 directions)",
+                   (long long)blocks, (long long)B, (long long)n_slices, CH_SLICE);
+    hipLaunchKernelGGL(chamfer_bwd_kernel, dim3((unsigned)blocks), dim3(CH_THREADS), 0, (hipStream_t)stream, px, nx,
+                       (long long)capx, py, ny, (long long)capy, idx_x, idx_y, dout, (int)n_slices, dpx, dpy);
+    DSVG_LAUNCH_CHECK("chamfer_bwd");
+    return 0;
+}
+
+extern "C" int dsvg_sample_points_bwd(const float* commands, int64_t B, int32_t G, int32_t L, int32_t n, const float* dpoints,
+                                      float* dargs, void* stream) {
+    DSVG_CHECK_ARG(commands && dpoints && dargs, "sample_points_bwd: null pointer");
+    DSVG_CHECK_ARG(n >= 2 && n <= 64, "sample_points_bwd: n = %d points per command, need 2..64", n);
+    DSVG_CHECK_ARG(B > 0 && B < (1ll << 31) && G >= 1 && L >= 1 && (int64_t)G * L <= SP_MAX_TOK,
+                   "sample_points_bwd: bad shape (B=%lld G=%d L=%d; G * L <= %d tokens per cloud)", (long long)B, G, L,
+                   SP_MAX_TOK);
+    const int64_t cap = (int64_t)G * ((int64_t)L * (n - 1) + 1);
+    DSVG_CHECK_ARG(cap < (1ll << 31), "sample_points_bwd: %lld points per cloud do not fit int32", (long long)cap);
+    hipLaunchKernelGGL(sample_points_bwd_kernel, dim3((unsigned)B), dim3(SP_THREADS), 0, (hipStream_t)stream, commands, G, L,
+                       n, (long long)cap, dpoints, dargs);
+    DSVG_LAUNCH_CHECK("sample_points_bwd");
     return 0;
 }

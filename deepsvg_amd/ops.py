@@ -1202,7 +1202,7 @@ def match_assign(cost, vis):
 
 
 # ------------------------------------------------------------------------------------------------
-# reconstruction error of decoded icons (difflib/tensor.py:191-230, difflib/loss.py:5-7), evaluation only
+# reconstruction error of decoded icons (difflib/tensor.py:191-230, difflib/loss.py:5-7) and its gradient
 # ------------------------------------------------------------------------------------------------
 def sample_points(commands, args, n=10, groups=1):
     """commands [B*groups, L] / args [B*groups, L, 11], both float32 or both int64 (read as they are) ->
@@ -1222,22 +1222,73 @@ def sample_points(commands, args, n=10, groups=1):
     return points, counts
 
 
-def chamfer(px, nx, py, ny):
-    """px f32 [B, capx, 2] with nx int32 [B] points in use, py f32 [B, capy, 2] with ny int32 [B] -> f32 [B]:
-    mean_i min_j |x_i - y_j| + mean_j min_i |x_i - y_j|, NaN where a cloud is empty; no distance matrix is built"""
+def _chk_clouds(px, nx, py, ny):
     _chk(px, nx, py, ny)
     for p, c in ((px, nx), (py, ny)):
         assert p.dtype == torch.float32 and p.dim() == 3 and p.shape[2] == 2 and p.is_contiguous()
         assert c.dtype == torch.int32 and c.shape == (p.shape[0],) and c.is_contiguous()
     assert px.shape[0] == py.shape[0]
+    return px.shape[0], px.shape[1], py.shape[1]
+
+
+def chamfer(px, nx, py, ny):
+    """px f32 [B, capx, 2] with nx int32 [B] points in use, py f32 [B, capy, 2] with ny int32 [B] -> f32 [B]:
+    mean_i min_j |x_i - y_j| + mean_j min_i |x_i - y_j|, NaN where a cloud is empty; no distance matrix is built"""
+    B, capx, capy = _chk_clouds(px, nx, py, ny)
     L = _l.load()
-    B, capx, capy = px.shape[0], px.shape[1], py.shape[1]
     out = torch.empty(B, dtype=torch.float32, device=px.device)
     ws_bytes = L.dsvg_chamfer_workspace_bytes(B, capx, capy)          # one partial sum per (icon, direction, 1,024 points)
     ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=px.device)
     _l.check(L.dsvg_chamfer(px.data_ptr(), nx.data_ptr(), capx, py.data_ptr(), ny.data_ptr(), capy, B, out.data_ptr(),
                             ws.data_ptr(), ws_bytes, _stream()), "dsvg_chamfer")
     return out
+
+
+def chamfer_nn(px, nx, py, ny):
+    """chamfer that also returns the arg-min indices -> (out f32 [B] with chamfer's bits, idx_x int32 [B, capx]: the point
+    of y nearest to x_i, idx_y int32 [B, capy]: the point of x nearest to y_j); ties go to the lowest index, entries past
+    the counts and those of icons with an empty cloud are not written"""
+    B, capx, capy = _chk_clouds(px, nx, py, ny)
+    L = _l.load()
+    out = torch.empty(B, dtype=torch.float32, device=px.device)
+    idx_x = torch.empty(B, capx, dtype=torch.int32, device=px.device)
+    idx_y = torch.empty(B, capy, dtype=torch.int32, device=px.device)
+    ws_bytes = L.dsvg_chamfer_workspace_bytes(B, capx, capy)
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=px.device)
+    _l.check(L.dsvg_chamfer_nn(px.data_ptr(), nx.data_ptr(), capx, py.data_ptr(), ny.data_ptr(), capy, B, out.data_ptr(),
+                               idx_x.data_ptr(), idx_y.data_ptr(), ws.data_ptr(), ws_bytes, _stream()), "dsvg_chamfer_nn")
+    return out, idx_x, idx_y
+
+
+def chamfer_bwd(px, nx, py, ny, idx_x, idx_y, dout):
+    """the clouds and indices of chamfer_nn, dout f32 [B] -> (dpx f32 [B, capx, 2], dpy f32 [B, capy, 2]): every row
+    written, zeros past the counts and on icons with an empty cloud (whatever dout holds there)"""
+    B, capx, capy = _chk_clouds(px, nx, py, ny)
+    _chk(idx_x, idx_y, dout)
+    assert idx_x.dtype == torch.int32 and idx_x.shape == (B, capx) and idx_x.is_contiguous()
+    assert idx_y.dtype == torch.int32 and idx_y.shape == (B, capy) and idx_y.is_contiguous()
+    assert dout.dtype == torch.float32 and dout.shape == (B,) and dout.is_contiguous()
+    dpx, dpy = torch.empty_like(px), torch.empty_like(py)
+    _l.check(_l.load().dsvg_chamfer_bwd(px.data_ptr(), nx.data_ptr(), capx, py.data_ptr(), ny.data_ptr(), capy, B,
+                                        idx_x.data_ptr(), idx_y.data_ptr(), dout.data_ptr(), dpx.data_ptr(), dpy.data_ptr(),
+                                        _stream()), "dsvg_chamfer_bwd")
+    return dpx, dpy
+
+
+def sample_points_bwd(commands, dpoints, n=10, groups=1):
+    """float32 commands [B*groups, L] and dpoints f32 [B, groups * (L * (n - 1) + 1), 2], laid out as sample_points returns
+    its points -> dargs f32 [B*groups, L, 11], every element written (integer inputs have no gradient)"""
+    _chk(commands, dpoints)
+    assert commands.dim() == 2 and commands.dtype == torch.float32 and commands.is_contiguous(), \
+        "sample_points_bwd: float32 commands [B*groups, L]"
+    assert groups >= 1 and commands.shape[0] % groups == 0
+    B, L = commands.shape[0] // groups, commands.shape[1]
+    assert dpoints.dtype == torch.float32 and dpoints.is_contiguous()
+    assert dpoints.shape == (B, groups * (L * (n - 1) + 1), 2), f"sample_points_bwd: dpoints {tuple(dpoints.shape)}"
+    dargs = torch.empty(commands.shape[0], L, 11, dtype=torch.float32, device=commands.device)
+    _l.check(_l.load().dsvg_sample_points_bwd(commands.data_ptr(), B, groups, L, int(n), dpoints.data_ptr(),
+                                              dargs.data_ptr(), _stream()), "dsvg_sample_points_bwd")
+    return dargs
 
 
 # ------------------------------------------------------------------------------------------------

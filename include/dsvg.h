@@ -44,8 +44,9 @@ extern "C" {
  * 11: two-stage configs with paths of 65..256 tokens: dsvg_build_masks_lens, dsvg_pack_tokens_lens, dsvg_packed_mean_fwd /
  *     bwd, dsvg_attention_long_packed_fwd / bwd, dsvg_attention_long_mfma_fwd / bwd added.
  * 12: dsvg_ffn_bwd removed (the fully fused FFN backward: no caller since round 2; dsvg_ffn_bwd_dx is the FFN backward's kernel).
- * 13: dsvg_sample_points / dsvg_chamfer (+ dsvg_chamfer_workspace_bytes) added (reconstruction error of decoded icons, evaluation only); DSVG_I64. */
-#define DSVG_ABI_VERSION 13
+ * 13: dsvg_sample_points / dsvg_chamfer (+ dsvg_chamfer_workspace_bytes) added (reconstruction error of decoded icons, evaluation only); DSVG_I64.
+ * 14: dsvg_chamfer_nn / dsvg_chamfer_bwd / dsvg_sample_points_bwd added (the gradient of the reconstruction error). */
+#define DSVG_ABI_VERSION 14
 
 const char* dsvg_last_error(void);
 int dsvg_version(void);
@@ -500,7 +501,7 @@ int dsvg_sample_rows(int32_t dtype, const void* logits, int64_t ld, int32_t grou
                      float temperature, const void* seed, uint32_t site, int32_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * Reconstruction error of decoded icons (csrc/metrics.hip), evaluation only: no gradients.
+ * Reconstruction error of decoded icons (csrc/metrics.hip): the forward pair, then its backward (below).
  *  sample_points: SVGTensor.sample_points (deepsvg/difflib/tensor.py:191-230), batched.  commands [B*G, L] and args
  *    [B*G, L, 11], both contiguous and both of dtype `itype` (DSVG_F32 as the dataset delivers them, DSVG_I64 as
  *    greedy_sample returns them; read as they are).  The G sequences of cloud b are concatenated in group order.  Per
@@ -523,6 +524,38 @@ int dsvg_sample_points(int32_t itype, const void* commands, const void* args, in
 int64_t dsvg_chamfer_workspace_bytes(int64_t B, int64_t capx, int64_t capy);
 int dsvg_chamfer(const float* px, const int32_t* nx, int64_t capx, const float* py, const int32_t* ny, int64_t capy,
                  int64_t B, float* out, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The gradient of the two above, as the reference's autograd gives it for SVGTensor.sample_points (two matmuls,
+ * deepsvg/difflib/tensor.py:220-228) and chamfer_loss (torch.cdist and two mins, deepsvg/difflib/loss.py:5-7), which
+ * notebooks/svgtensor.ipynb optimises Bezier parameters through.  No distance matrix, no atomics: bit-reproducible.
+ *  chamfer_nn: dsvg_chamfer (the same `out` bit for bit, the same workspace) that also writes the arg-min indices
+ *    idx_x int32 [B, capx]: idx_x[b, i] = argmin_j |x_i - y_j| and idx_y int32 [B, capy]: idx_y[b, j] = argmin_i
+ *    |x_i - y_j|, for the points in use; of equidistant candidates the lowest index wins.  Entries past the counts, and
+ *    those of an icon with an empty cloud, are not written.
+ *  chamfer_bwd (loss.py:5-7 differentiated): with j*(i) = idx_x, i*(j) = idx_y and u(a, b) = (a - b) / |a - b|, u = 0
+ *    where a == b (so chamfer(x, x) has an exactly zero gradient, where the reference's matmul-form cdist backward is
+ *    undefined),
+ *      dpx[b, i] = dout[b] * ( u(x_i, y_j*(i)) / nx[b]  -  sum over {j : i*(j) = i} of u(y_j, x_i) / ny[b] )
+ *    and dpy symmetrically (the same code on swapped pointers: d chamfer(x, y) / dx == the second gradient of
+ *    chamfer(y, x) bit for bit).  One launch, one workgroup per (icon, direction, slice of 1,024 points); the terms of a
+ *    point are added in ascending j.  dpx fp32 [B, capx, 2], dpy fp32 [B, capy, 2]: ALL rows are written, zeros past the
+ *    counts; an icon with an empty cloud (forward NaN) gets zero rows whatever dout[b] holds.  Indices are clamped into
+ *    their cloud.
+ *  sample_points_bwd (tensor.py:191-230 differentiated; DSVG_F32 commands only - integer inputs have no gradient):
+ *    dpoints fp32 [B, cap, 2] laid out as dsvg_sample_points writes `points` (entries past the counts are not read) ->
+ *    dargs fp32 [B*G, L, 11], every element written.  A drawing command at row t with its samples z_k = k / (n - 1)
+ *    receives, for `c`: sum 3 (1 - z)^2 z dP in 5:7, sum 3 (1 - z) z^2 dP in 7:9, sum z^3 dP in 9:11; for `l`: sum z dP in
+ *    9:11.  Its start point's share (sum (1 - z)^3 dP for `c`, sum (1 - z) dP for `l`) goes to columns 9:11 of row t - 1
+ *    WHATEVER that row holds (tensor.py:75-82: an m or SOS row gets a gradient there); row 0 starts at the constant (0, 0).
+ *    Everything else is zero.  Sums in float64.  Same limits as the forward: 2 <= n <= 64, G * L <= 2048. */
+int dsvg_chamfer_nn(const float* px, const int32_t* nx, int64_t capx, const float* py, const int32_t* ny, int64_t capy,
+                    int64_t B, float* out, int32_t* idx_x, int32_t* idx_y, void* workspace, int64_t workspace_bytes,
+                    void* stream);
+int dsvg_chamfer_bwd(const float* px, const int32_t* nx, int64_t capx, const float* py, const int32_t* ny, int64_t capy,
+                     int64_t B, const int32_t* idx_x, const int32_t* idx_y, const float* dout, float* dpx, float* dpy,
+                     void* stream);
+int dsvg_sample_points_bwd(const float* commands, int64_t B, int32_t G, int32_t L, int32_t n, const float* dpoints,
+                           float* dargs, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The argument head fused with its consumers (csrc/head_fused.hip): args_fcn = Linear(256 -> n_args *

@@ -7,6 +7,9 @@ of S + 2 = 32 tokens), n = 10 points per command:
                       points in every cloud: the most these shapes give, and equal work in every workgroup)
   the reference's way on the same GPU: a loop over icons of torch.cdist -> min -> mean (deepsvg/difflib/loss.py:5-7 restated)
                       over the kernel's points
+  the backward legs   ops.chamfer_nn (next to ops.chamfer: the same sweep with the arg-min kept), ops.chamfer_bwd,
+                      ops.sample_points_bwd, one step of metrics.refine's loop (sample_points -> chamfer -> backward -> Adam),
+                      and the reference's way again: the per-icon torch.cdist loop with autograd through it
 
 HIP events around `inner` back-to-back calls, median of 20 such runs after warm-up.  The VALU floor quoted for the Chamfer
 launch is pairs * 4.5 vector instructions (2 subtractions, multiply, fused multiply-add, half a 3-way minimum: the kernel's inner
@@ -19,7 +22,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from deepsvg_amd import ops                          # noqa: E402
+from deepsvg_amd import metrics, ops                 # noqa: E402
 from deepsvg_amd.synthetic import make_batch         # noqa: E402
 
 N, G, S, NPTS = 512, 8, 30, 10
@@ -97,6 +100,51 @@ def main():
               f"kernel; largest matrix {max(a * b for a, b in zip(nxl, nyl)) * 4 / 1e6:.1f} MB, all {N} at once would be "
               f"{sum(a * b for a, b in zip(nxl, nyl)) * 4 / 1e9:.2f} GB; max |kernel - fp32 cdist| {float((got - want).abs().max()):.2e}")
         print(f"[{tag}] mean Chamfer distance of the two batches {float(got.mean()):.4f}")
+        # ---- the backward legs ----
+        med_nn, lo, hi = timed(lambda: ops.chamfer_nn(px, nx, py, ny), inner=10)
+        print(f"[{tag}] chamfer_nn: {med_nn * 1e3:8.1f} us [{lo * 1e3:.1f} .. {hi * 1e3:.1f}] = {med_nn / med:.2f} x chamfer")
+        out_nn, idx_x, idx_y = ops.chamfer_nn(px, nx, py, ny)
+        assert torch.equal(out_nn.view(torch.int32), got.view(torch.int32)), "chamfer_nn and chamfer differ in bits"
+        dout = torch.ones(N, device=dev)
+        med_b, lo, hi = timed(lambda: ops.chamfer_bwd(px, nx, py, ny, idx_x, idx_y, dout), inner=10)
+        print(f"[{tag}] chamfer_bwd: {med_b * 1e3:8.1f} us [{lo * 1e3:.1f} .. {hi * 1e3:.1f}] = {med_b / med:.2f} x chamfer")
+        dpx, _ = ops.chamfer_bwd(px, nx, py, ny, idx_x, idx_y, dout)
+        med_s, lo, hi = timed(lambda: ops.sample_points_bwd(c32, dpx, n=NPTS, groups=G), inner=20)
+        print(f"[{tag}] sample_points_bwd: {med_s * 1e3:8.1f} us [{lo * 1e3:.1f} .. {hi * 1e3:.1f}]  reads {dpx.numel() * 4 / 1e6:.1f} MB of "
+              f"point gradients, writes {a32.numel() * 4 / 1e6:.1f} MB")
+        ref = a32.view(N, G, S + 2, 11).clone().requires_grad_(True)
+        opt = torch.optim.Adam([ref], lr=0.1)
+
+        def refine_step():
+            opt.zero_grad(set_to_none=True)
+            metrics.chamfer_loss(ca, ref, py, ny, NPTS)["loss"].backward()
+            opt.step()
+        med_r, lo, hi = timed(refine_step, inner=5)
+        print(f"[{tag}] one refine step (sample_points, chamfer_nn, chamfer_bwd, sample_points_bwd, masked mean, Adam): "
+              f"{med_r * 1e3:8.1f} us [{lo * 1e3:.1f} .. {hi * 1e3:.1f}]")
+        grown = []
+        for _ in range(2):                              # (second pass: code objects and the allocator's pools are warm)
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            before = torch.cuda.memory_allocated()
+            o, ix, iy = ops.chamfer_nn(px, nx, py, ny)
+            gx, gy = ops.chamfer_bwd(px, nx, py, ny, ix, iy, dout)
+            torch.cuda.synchronize()
+            grown.append(torch.cuda.max_memory_allocated() - before)
+        print(f"[{tag}] chamfer_nn + chamfer_bwd allocate {grown[-1] / 1e6:.2f} MB: indices {(ix.numel() + iy.numel()) * 4 / 1e6:.2f} MB, "
+              f"gradients {(gx.numel() + gy.numel()) * 4 / 1e6:.2f} MB, out + workspace the rest")
+        pxl = px.clone().requires_grad_(True)
+
+        def torch_loop_backward():
+            pxl.grad = None
+            chamfer_torch_loop(pxl, nxl, py, nyl).sum().backward()
+        med_tb, lo_t, hi_t = timed(torch_loop_backward, inner=1, runs=5, warmup=1)
+        torch_loop_backward()
+        live = (torch.arange(px.shape[1], device=dev).unsqueeze(0) < nx.unsqueeze(1)).unsqueeze(-1)
+        diff = torch.where(live, (pxl.grad - dpx).abs(), torch.zeros_like(dpx))
+        print(f"[{tag}] torch.cdist loop, forward + autograd backward (5 runs): {med_tb:8.2f} ms [{lo_t:.2f} .. {hi_t:.2f}] = "
+              f"{med_tb / (med_nn + med_b):.0f} x chamfer_nn + chamfer_bwd; max |kernel - fp32 cdist autograd| on d / d points "
+              f"{float(diff.max()):.2e}, above 1e-5 in {int((diff > 1e-5).sum())} of {int(live.sum()) * 2} entries")
 
 
 if __name__ == "__main__":
