@@ -5,6 +5,7 @@ Public surface mirrors the reference (alexandre01/deepsvg):
     deepsvg_amd.SVGLoss         <->  deepsvg.model.loss.SVGLoss
     deepsvg_amd.config.*        <->  deepsvg.model.config.*
     deepsvg_amd.metrics         <->  deepsvg.difflib: SVGTensor.sample_points + chamfer_loss (reconstruction error)
+                                     and the other losses of difflib/loss.py: svg_emd_loss, svg_length_loss, continuity_loss
 """
 # (No process-wide side effects on import.  The data-parallel hipGraph step wants GPU_MAX_HW_QUEUES=6 in the environment BEFORE
 # the HIP runtime comes up - see trainer.HW_QUEUES_NOTE; bench.py sets it, TrainStep warns when a data-parallel trainer

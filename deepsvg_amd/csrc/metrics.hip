@@ -512,6 +512,311 @@ __global__ __launch_bounds__(CH_THREADS) void chamfer_bwd_kernel(const float* __
 inline int64_t chamfer_slices(int64_t capx, int64_t capy) {
     return ((capx > capy ? capx : capy) + CH_SLICE - 1) / CH_SLICE;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The ordered losses of deepsvg/difflib/loss.py: svg_emd_loss (:21-51) and the polyline length behind svg_length_loss /
+// continuity_loss (:10-18).  Lengths, the orientation sum and the shift sums are float64 so that every choice (flip, match,
+// shift) is a property of the input and not of a summation order.
+constexpr int EM_THREADS = 256;
+constexpr int EM_WAVES = EM_THREADS / 64;
+constexpr int EM_PER = 4;                              // consecutive target points of a chunk per thread
+constexpr int EM_CHUNK = EM_THREADS * EM_PER;          // target points per chunk of the arc-length scan: 1,024
+constexpr int EM_SHIFTS = 256;                         // shifts per workgroup of emd_shift_kernel, one per thread
+constexpr int EM_KTILE = 1024;                         // pred points per LDS tile of emd_shift_kernel
+constexpr int EM_MAX_N = 65536;                        // pred points per cloud (the shift search is quadratic in them)
+
+__device__ __forceinline__ double segment_length(float2 a, float2 b) {
+    const double dx = (double)b.x - (double)a.x, dy = (double)b.y - (double)a.y;
+    return sqrt(dx * dx + dy * dy);
+}
+
+// the sum of v over the workgroup, in a fixed order (butterfly inside the wave, the waves ascending), in every thread
+__device__ __forceinline__ double block_sum_f64(double v, double* __restrict__ red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();                                   // red of a call before has been read
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double tot = 0.0;
+#pragma unroll
+    for (int w = 0; w < EM_WAVES; ++w) tot += red[w];
+    return tot;
+}
+
+// v[r] -> the inclusive prefix sum over the workgroup's EM_CHUNK items (thread tid holds items 4 tid .. 4 tid + 3): the sums
+// inside a thread, plus the totals of the threads before it added from left to right.  What a thread starts from is the
+// last sum of the thread before it, bit for bit, so the sums never decrease, and the returned chunk total is the last
+// item's sum.  sc: EM_THREADS doubles.
+__device__ __forceinline__ double block_scan_f64(double (&v)[EM_PER], double* __restrict__ sc) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int r = 1; r < EM_PER; ++r) v[r] += v[r - 1];
+    __syncthreads();                                   // sc of a call before has been read
+    sc[tid] = v[EM_PER - 1];
+    __syncthreads();
+    double run = 0.0, before = 0.0;
+    for (int q = 0; q < EM_THREADS; ++q) {             // the same address in every lane
+        if (q == tid) before = run;
+        run += sc[q];
+    }
+#pragma unroll
+    for (int r = 0; r < EM_PER; ++r) v[r] += before;
+    return run;
+}
+
+// the first slot in [lo, hi] whose value is >= u; d[hi] >= u is known
+__device__ __forceinline__ int lower_slot(const double* __restrict__ d, int lo, int hi, double u) {
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (d[mid] >= u) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+// Workgroup b: orientation of the target, its normalised arc-length distribution D (chunk by chunk, never stored), and
+// for every pred point i the target point whose D is nearest to u_i = i / (n - 1) (the lowest index of a tie):
+//   match[b, i] = that point's index into the target AS PASSED, t[b, i] = its coordinates.
+// An icon with an empty cloud writes nothing.
+__global__ __launch_bounds__(EM_THREADS) void emd_match_kernel(const int32_t* __restrict__ nx, long long capx,
+                                                               const float* __restrict__ py, const int32_t* __restrict__ ny,
+                                                               long long capy, int32_t* __restrict__ match,
+                                                               float* __restrict__ t) {
+    __shared__ double Dl[EM_CHUNK + 1];                // slot 0: the last D of the chunk before; slot 1 + q: D of item j0 + q
+    __shared__ double sc[EM_THREADS];
+    __shared__ double red[EM_WAVES];
+    __shared__ double total_sh;
+    const long long b = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int n = chamfer_count(nx, b, capx), m = chamfer_count(ny, b, capy);
+    if (n == 0 || m == 0) return;                      // (block-uniform)
+    const float2* y = reinterpret_cast<const float2*>(py) + b * capy;
+    int32_t* mt = match + b * capx;
+    float2* tt = reinterpret_cast<float2*>(t) + b * capx;
+
+    // orientation: the open polyline's shoelace sum (utils.py:52-60); not (A > 0) reverses
+    double a = 0.0;
+    for (int j = tid; j < m - 1; j += EM_THREADS) {
+        const float2 p = y[j], q = y[j + 1];
+        a += (double)p.x * (double)q.y - (double)q.x * (double)p.y;
+    }
+    const bool flip = !(block_sum_f64(a, red) > 0.0);
+    auto yo = [&](int j) { return y[flip ? m - 1 - j : j]; };
+    auto item = [&](int j) { return j >= 1 && j < m ? segment_length(yo(j - 1), yo(j)) : 0.0; };
+
+    // total length: the scan below without its stores, taken at the last point, so that the last D is total / total = 1
+    double head = 0.0;
+    for (int j0 = 0; j0 < m; j0 += EM_CHUNK) {
+        double v[EM_PER];
+#pragma unroll
+        for (int r = 0; r < EM_PER; ++r) v[r] = item(j0 + tid * EM_PER + r);
+        const double tot = block_scan_f64(v, sc);
+#pragma unroll
+        for (int r = 0; r < EM_PER; ++r)
+            if (j0 + tid * EM_PER + r == m - 1) total_sh = head + v[r];
+        head += tot;
+    }
+    __syncthreads();
+    const double total = total_sh;
+    if (!(total > 0.0)) {                              // one point, or all points the same: everything matches index 0
+        const int orig = flip ? m - 1 : 0;
+        for (int i = tid; i < n; i += EM_THREADS) { mt[i] = orig; tt[i] = y[orig]; }
+        return;
+    }
+    const double un = n > 1 ? (double)(n - 1) : 1.0;
+    double carry = 0.0, prev_last = -1.0;              // prev_last < 0 <= every u: the first chunk has nothing before it
+    int carry_run = 0;                                 // the first index whose D equals prev_last
+    for (int j0 = 0; j0 < m; j0 += EM_CHUNK) {
+        double v[EM_PER];
+#pragma unroll
+        for (int r = 0; r < EM_PER; ++r) v[r] = item(j0 + tid * EM_PER + r);
+        const double tot = block_scan_f64(v, sc);
+        __syncthreads();                               // Dl of the chunk before has been read
+        const int cnt = min(EM_CHUNK, m - j0);
+        if (tid == 0) Dl[0] = prev_last;
+#pragma unroll
+        for (int r = 0; r < EM_PER; ++r) {
+            const int q = tid * EM_PER + r;
+            if (q < cnt) Dl[1 + q] = (carry + v[r]) / total;
+        }
+        __syncthreads();
+        const double lo_d = Dl[0], hi_d = Dl[cnt];
+        for (int i = tid; i < n; i += EM_THREADS) {
+            const double u = (double)i / un;
+            if (!(u > lo_d && u <= hi_d)) continue;
+            const int lb = lower_slot(Dl, 1, cnt, u);
+            int g = j0 + lb - 1;
+            if (!(j0 == 0 && lb == 1) && u - Dl[lb - 1] <= Dl[lb] - u) {      // the point below is as near: lowest index
+                const int fa = lower_slot(Dl, 0, lb - 1, Dl[lb - 1]);           // ... of the run of equal D it ends
+                g = fa == 0 ? carry_run : j0 + fa - 1;
+            }
+            const int orig = flip ? m - 1 - g : g;
+            mt[i] = orig;
+            tt[i] = y[orig];
+        }
+        const int fl = lower_slot(Dl, 0, cnt, hi_d);
+        carry_run = fl == 0 ? carry_run : j0 + fl - 1;
+        prev_last = hi_d;
+        carry += tot;
+    }
+}
+
+// Workgroup (icon b, block of EM_SHIFTS shifts): thread s walks S(s) = sum_k |x_k - t_{(k + s) mod n}| in ascending k, float64
+// running sum of fp32 terms (one sqrtf each).  x and the window of t a tile needs go through LDS: x[k] is a broadcast,
+// t[k + s] consecutive addresses across the lanes.  bmin / barg [b, block] take the block's minimum and its lowest shift.
+__global__ __launch_bounds__(EM_SHIFTS) void emd_shift_kernel(const float* __restrict__ px, const int32_t* __restrict__ nx,
+                                                              long long capx, const int32_t* __restrict__ ny, long long capy,
+                                                              const float* __restrict__ t, int n_blocks,
+                                                              double* __restrict__ bmin, int32_t* __restrict__ barg) {
+    __shared__ float2 xs[EM_KTILE];
+    __shared__ float2 ts[EM_KTILE + EM_SHIFTS];
+    __shared__ double rs[EM_WAVES];
+    __shared__ int ra[EM_WAVES];
+    const long long blk = blockIdx.x;
+    const long long b = blk / n_blocks;
+    const int s0 = (int)(blk % n_blocks) * EM_SHIFTS;
+    const int n = chamfer_count(nx, b, capx);
+    if (s0 >= n || chamfer_count(ny, b, capy) == 0) return;          // (block-uniform)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float2* x = reinterpret_cast<const float2*>(px) + b * capx;
+    const float2* tg = reinterpret_cast<const float2*>(t) + b * capx;
+    const int s = s0 + tid;
+    double sum = 0.0;
+    for (int k0 = 0; k0 < n; k0 += EM_KTILE) {
+        const int kc = min(EM_KTILE, n - k0);
+        if (k0) __syncthreads();                       // the tiles of the step before have been read
+        for (int i = tid; i < kc; i += EM_SHIFTS) xs[i] = x[k0 + i];
+        const int base = (k0 + s0) % n;
+        for (int i = tid; i < kc + EM_SHIFTS - 1; i += EM_SHIFTS) ts[i] = tg[(base + i) % n];
+        __syncthreads();
+        if (s < n) {
+#pragma unroll 4
+            for (int k = 0; k < kc; ++k) {
+                const float2 p = xs[k], q = ts[k + tid];
+                const float dx = p.x - q.x, dy = p.y - q.y;
+                sum += (double)sqrtf(fmaf(dx, dx, dy * dy));
+            }
+        }
+    }
+    // (minimum, lowest shift) of the block
+    double best = s < n ? sum : INFINITY;
+    int arg = s < n ? s : 0x7fffffff;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ob = __shfl_xor(best, o, 64);
+        const int oa = __shfl_xor(arg, o, 64);
+        if (ob < best || (ob == best && oa < arg)) { best = ob; arg = oa; }
+    }
+    if (lane == 0) { rs[wave] = best; ra[wave] = arg; }
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int w = 1; w < EM_WAVES; ++w)
+            if (rs[w] < best || (rs[w] == best && ra[w] < arg)) { best = rs[w]; arg = ra[w]; }
+        bmin[blk] = best;
+        barg[blk] = arg;
+    }
+}
+
+// Workgroup b: the blocks in ascending order with strict < give (S(s*), s*); loss = (S(s*) + 9 |x_0 - t_{s*}| with the
+// first-point weight) / n, matched[k] = match[(k + s*) mod n], -1 past the count.  n == 0: loss 0 (loss.py:25-26);
+// n > 0 with an empty target: NaN.  shift is 0 and matched -1 in both.
+__global__ __launch_bounds__(EM_THREADS) void emd_finish_kernel(const float* __restrict__ px, const int32_t* __restrict__ nx,
+                                                                long long capx, const int32_t* __restrict__ ny, long long capy,
+                                                                const float* __restrict__ t, const int32_t* __restrict__ match,
+                                                                const double* __restrict__ bmin, const int32_t* __restrict__ barg,
+                                                                int n_blocks, int weighted, float* __restrict__ out,
+                                                                int32_t* __restrict__ shift, int32_t* __restrict__ matched) {
+    const long long b = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int n = chamfer_count(nx, b, capx), m = chamfer_count(ny, b, capy);
+    int32_t* mo = matched + b * capx;
+    if (n == 0 || m == 0) {                            // (block-uniform)
+        if (tid == 0) { out[b] = n == 0 ? 0.f : __builtin_nanf(""); shift[b] = 0; }
+        for (long long k = tid; k < capx; k += EM_THREADS) mo[k] = -1;
+        return;
+    }
+    double best = bmin[b * n_blocks];                  // every thread scans: the same address in every lane
+    int s = barg[b * n_blocks];
+    for (int q = 1; q < (n + EM_SHIFTS - 1) / EM_SHIFTS; ++q) {
+        const double v = bmin[b * n_blocks + q];
+        if (v < best) { best = v; s = barg[b * n_blocks + q]; }
+    }
+    s = min(max(s, 0), n - 1);
+    if (tid == 0) {
+        if (weighted) {
+            const float2 p = reinterpret_cast<const float2*>(px)[b * capx], q = reinterpret_cast<const float2*>(t)[b * capx + s];
+            const float dx = p.x - q.x, dy = p.y - q.y;
+            best += 9.0 * (double)sqrtf(fmaf(dx, dx, dy * dy));
+        }
+        out[b] = (float)(best / (double)n);
+        shift[b] = s;
+    }
+    const int32_t* mt = match + b * capx;
+    for (long long k = tid; k < capx; k += EM_THREADS) {
+        int j = (int)k + s;
+        if (j >= n) j -= n;
+        mo[k] = k < n ? mt[j] : -1;
+    }
+}
+
+// dpx[b, k] = dout[b] w_k (x_k - t_{(k + s*) mod n}) / (|...| n), one thread per row; zero rows past the count and on an
+// icon with an empty cloud (whatever dout[b] holds)
+__global__ __launch_bounds__(256) void emd_bwd_kernel(const float* __restrict__ px, const int32_t* __restrict__ nx, long long capx,
+                                                      const int32_t* __restrict__ ny, const float* __restrict__ t,
+                                                      const int32_t* __restrict__ shift, const float* __restrict__ dout,
+                                                      int weighted, long long rows, float* __restrict__ dpx) {
+    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    const long long b = r / capx;
+    const int k = (int)(r - b * capx);
+    const int n = chamfer_count(nx, b, capx);
+    float2 g = make_float2(0.f, 0.f);
+    if (k < n && ny[b] > 0) {
+        int j = k + min(max(shift[b], 0), n - 1);
+        if (j >= n) j -= n;
+        const float2 u = chamfer_unit_over(reinterpret_cast<const float2*>(px)[r], reinterpret_cast<const float2*>(t)[b * capx + j],
+                                           (float)n);
+        const float d = dout[b] * (weighted && k == 0 ? 10.f : 1.f);
+        g = make_float2(d * u.x, d * u.y);
+    }
+    reinterpret_cast<float2*>(dpx)[r] = g;
+}
+
+// Workgroup b: L = sum_i |p_{i+1} - p_i| over the points in use, float64 in a fixed order
+__global__ __launch_bounds__(EM_THREADS) void polyline_length_kernel(const float* __restrict__ p, const int32_t* __restrict__ n,
+                                                                     long long cap, float* __restrict__ out) {
+    __shared__ double red[EM_WAVES];
+    const long long b = blockIdx.x;
+    const int cnt = chamfer_count(n, b, cap);
+    const float2* x = reinterpret_cast<const float2*>(p) + b * cap;
+    double a = 0.0;
+    for (int i = threadIdx.x; i < cnt - 1; i += EM_THREADS) a += segment_length(x[i], x[i + 1]);
+    const double tot = block_sum_f64(a, red);
+    if (threadIdx.x == 0) out[b] = (float)tot;
+}
+
+// dp[b, i] = dout[b] (u(p_i, p_{i-1}) - u(p_{i+1}, p_i)), u = 0 on a zero-length segment; zero rows past the count
+__global__ __launch_bounds__(256) void polyline_length_bwd_kernel(const float* __restrict__ p, const int32_t* __restrict__ n,
+                                                                  long long cap, const float* __restrict__ dout, long long rows,
+                                                                  float* __restrict__ dp) {
+    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    const long long b = r / cap;
+    const int i = (int)(r - b * cap);
+    const int cnt = chamfer_count(n, b, cap);
+    const float2* x = reinterpret_cast<const float2*>(p);
+    float2 g = make_float2(0.f, 0.f);
+    if (i < cnt) {
+        const float2 c = x[r];
+        if (i > 0) { const float2 u = chamfer_unit_over(c, x[r - 1], 1.f); g.x += u.x; g.y += u.y; }
+        if (i + 1 < cnt) { const float2 u = chamfer_unit_over(x[r + 1], c, 1.f); g.x -= u.x; g.y -= u.y; }
+        const float d = dout[b];
+        g = make_float2(d * g.x, d * g.y);
+    }
+    reinterpret_cast<float2*>(dp)[r] = g;
+}
+
+inline int64_t emd_blocks(int64_t capx) { return (capx + EM_SHIFTS - 1) / EM_SHIFTS; }
 }  // namespace
 
 extern "C" int dsvg_sample_points(int32_t itype, const void* commands, const void* args, int64_t B, int32_t G, int32_t L,
@@ -612,5 +917,81 @@ extern "C" int dsvg_sample_points_bwd(const float* commands, int64_t B, int32_t 
     hipLaunchKernelGGL(sample_points_bwd_kernel, dim3((unsigned)B), dim3(SP_THREADS), 0, (hipStream_t)stream, commands, G, L,
                        n, (long long)cap, dpoints, dargs);
     DSVG_LAUNCH_CHECK("sample_points_bwd");
+    return 0;
+}
+
+extern "C" int64_t dsvg_emd_workspace_bytes(int64_t B, int64_t capx) {
+    if (B <= 0 || capx <= 0) return 0;
+    return B * emd_blocks(capx) * (int64_t)(sizeof(double) + sizeof(int32_t)) + B * capx * (int64_t)sizeof(int32_t);
+}
+
+extern "C" int dsvg_emd(const float* px, const int32_t* nx, int64_t capx, const float* py, const int32_t* ny, int64_t capy,
+                        int64_t B, int32_t first_point_weight, float* out, int32_t* shift, int32_t* matched, float* t,
+                        void* workspace, int64_t workspace_bytes, void* stream) {
+    DSVG_CHECK_ARG(px && nx && py && ny && out && shift && matched && t && workspace, "emd: null pointer");
+    DSVG_CHECK_ARG(B > 0 && B < (1ll << 31) && capx > 0 && capy > 0 && capy < (1ll << 31),
+                   "emd: bad shape (B=%lld capx=%lld capy=%lld; target clouds hold 1 .. 2^31 - 1 points)", (long long)B,
+                   (long long)capx, (long long)capy);
+    DSVG_CHECK_ARG(capx <= EM_MAX_N, "emd: capx = %lld, a pred cloud holds at most %d points", (long long)capx, EM_MAX_N);
+    const int64_t n_blocks = emd_blocks(capx), blocks = B * n_blocks;
+    DSVG_CHECK_ARG(blocks < (1ll << 31), "emd: %lld workgroups (B=%lld, %lld blocks of %d shifts)", (long long)blocks,
+                   (long long)B, (long long)n_blocks, EM_SHIFTS);
+    DSVG_CHECK_ARG(workspace_bytes >= dsvg_emd_workspace_bytes(B, capx) && ((uintptr_t)workspace & 7) == 0,
+                   "emd: workspace of %lld bytes, need %lld (8-byte aligned)", (long long)workspace_bytes,
+                   (long long)dsvg_emd_workspace_bytes(B, capx));
+    double* bmin = (double*)workspace;                 // [B, n_blocks], then barg int32 [B, n_blocks], match int32 [B, capx]
+    int32_t* barg = (int32_t*)(bmin + blocks);
+    int32_t* match = barg + blocks;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(emd_match_kernel, dim3((unsigned)B), dim3(EM_THREADS), 0, st, nx, (long long)capx, py, ny,
+                       (long long)capy, match, t);
+    DSVG_LAUNCH_CHECK("emd_match");
+    hipLaunchKernelGGL(emd_shift_kernel, dim3((unsigned)blocks), dim3(EM_SHIFTS), 0, st, px, nx, (long long)capx, ny,
+                       (long long)capy, (const float*)t, (int)n_blocks, bmin, barg);
+    DSVG_LAUNCH_CHECK("emd_shift");
+    hipLaunchKernelGGL(emd_finish_kernel, dim3((unsigned)B), dim3(EM_THREADS), 0, st, px, nx, (long long)capx, ny,
+                       (long long)capy, (const float*)t, (const int32_t*)match, (const double*)bmin, (const int32_t*)barg,
+                       (int)n_blocks, first_point_weight ? 1 : 0, out, shift, matched);
+    DSVG_LAUNCH_CHECK("emd_finish");
+    return 0;
+}
+
+extern "C" int dsvg_emd_bwd(const float* px, const int32_t* nx, int64_t capx, const int32_t* ny, const float* t,
+                            const int32_t* shift, const float* dout, int32_t first_point_weight, int64_t B, float* dpx,
+                            void* stream) {
+    DSVG_CHECK_ARG(px && nx && ny && t && shift && dout && dpx, "emd_bwd: null pointer");
+    DSVG_CHECK_ARG(B > 0 && B < (1ll << 31) && capx > 0, "emd_bwd: bad shape (B=%lld capx=%lld)", (long long)B, (long long)capx);
+    DSVG_CHECK_ARG(capx <= EM_MAX_N, "emd_bwd: capx = %lld, a pred cloud holds at most %d points", (long long)capx, EM_MAX_N);
+    const int64_t rows = B * capx;
+    DSVG_CHECK_ARG((rows + 255) / 256 < (1ll << 31), "emd_bwd: %lld rows (B=%lld capx=%lld)", (long long)rows, (long long)B,
+                   (long long)capx);
+    hipLaunchKernelGGL(emd_bwd_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, px, nx,
+                       (long long)capx, ny, t, shift, dout, first_point_weight ? 1 : 0, (long long)rows, dpx);
+    DSVG_LAUNCH_CHECK("emd_bwd");
+    return 0;
+}
+
+extern "C" int dsvg_polyline_length(const float* p, const int32_t* n, int64_t cap, int64_t B, float* out, void* stream) {
+    DSVG_CHECK_ARG(p && n && out, "polyline_length: null pointer");
+    DSVG_CHECK_ARG(B > 0 && B < (1ll << 31) && cap > 0 && cap < (1ll << 31),
+                   "polyline_length: bad shape (B=%lld cap=%lld; clouds hold 1 .. 2^31 - 1 points)", (long long)B, (long long)cap);
+    hipLaunchKernelGGL(polyline_length_kernel, dim3((unsigned)B), dim3(EM_THREADS), 0, (hipStream_t)stream, p, n, (long long)cap,
+                       out);
+    DSVG_LAUNCH_CHECK("polyline_length");
+    return 0;
+}
+
+extern "C" int dsvg_polyline_length_bwd(const float* p, const int32_t* n, int64_t cap, int64_t B, const float* dout, float* dp,
+                                        void* stream) {
+    DSVG_CHECK_ARG(p && n && dout && dp, "polyline_length_bwd: null pointer");
+    DSVG_CHECK_ARG(B > 0 && B < (1ll << 31) && cap > 0 && cap < (1ll << 31),
+                   "polyline_length_bwd: bad shape (B=%lld cap=%lld; clouds hold 1 .. 2^31 - 1 points)", (long long)B,
+                   (long long)cap);
+    const int64_t rows = B * cap;
+    DSVG_CHECK_ARG((rows + 255) / 256 < (1ll << 31), "polyline_length_bwd: %lld rows (B=%lld cap=%lld)", (long long)rows,
+                   (long long)B, (long long)cap);
+    hipLaunchKernelGGL(polyline_length_bwd_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, n,
+                       (long long)cap, dout, (long long)rows, dp);
+    DSVG_LAUNCH_CHECK("polyline_length_bwd");
     return 0;
 }

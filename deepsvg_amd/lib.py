@@ -15,7 +15,7 @@ DSVG_BF16 = 1
 DSVG_I64 = 2          # input dtype of dsvg_sample_points only
 # == DSVG_ABI_VERSION of include/dsvg.h at the time SIGNATURES below was written: load() refuses a library built from another
 # header (a stale .so with the old argument lists would otherwise be called with a stream where a size is expected)
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 c_i32, c_i64, c_u32, c_f32 = C.c_int32, C.c_int64, C.c_uint32, C.c_float
 vp = C.c_void_p
@@ -158,6 +158,11 @@ SIGNATURES = {
     "dsvg_chamfer_nn": (c_i32, [vp, vp, c_i64, vp, vp, c_i64, c_i64, vp, vp, vp, vp, c_i64, vp]),
     "dsvg_chamfer_bwd": (c_i32, [vp, vp, c_i64, vp, vp, c_i64, c_i64, vp, vp, vp, vp, vp, vp]),
     "dsvg_sample_points_bwd": (c_i32, [vp, c_i64, c_i32, c_i32, c_i32, vp, vp, vp]),
+    "dsvg_emd_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "dsvg_emd": (c_i32, [vp, vp, c_i64, vp, vp, c_i64, c_i64, c_i32, vp, vp, vp, vp, vp, c_i64, vp]),
+    "dsvg_emd_bwd": (c_i32, [vp, vp, c_i64, vp, vp, vp, vp, c_i32, c_i64, vp, vp]),
+    "dsvg_polyline_length": (c_i32, [vp, vp, c_i64, c_i64, vp, vp]),
+    "dsvg_polyline_length_bwd": (c_i32, [vp, vp, c_i64, c_i64, vp, vp, vp]),
     "dsvg_ffn_pack_bytes": (c_i64, [c_i32, c_i32]),
     "dsvg_ffn_pack": (c_i32, [vp, vp, c_i32, c_i32, c_i32, vp, vp, vp, vp, vp]),
     "dsvg_ffn_fwd": (c_i32, [vp, vp, vp, vp, vp, vp, vp, vp, c_i64, c_f32, c_f32, c_u32, c_u32, vp, c_i32, vp]),

@@ -11,13 +11,23 @@ a zero gradient), the start point of a drawing command is the end position of th
 and an icon with an empty cloud gets a zero gradient.  No distance matrix, no atomics: bit-reproducible.  int64 inputs,
 calls under ``torch.no_grad()`` and inputs that do not require grad take the forward-only kernels, as before.
 `reconstruction_error` stays an evaluation: no gradients.
+
+The other losses of deepsvg/difflib/loss.py are here as well, batched in the same way.  `emd` is ``svg_emd_loss``
+(loss.py:21-51), the ORDERED point loss that the notebook's optimisation cell actually minimises: the target is oriented
+(``make_clockwise``), sampled at the pred cloud's uniform arc-length fractions, and the cyclic shift with the smallest mean
+point-to-point distance is taken - a curve that visits the right places in the wrong order does not score well, as it does
+under the order-free Chamfer distance.  Lengths and the shift sums are float64 on the device, so orientation, matching and
+shift are properties of the input (the lowest index wins every tie); the gradient is with respect to the PRED cloud only,
+the target is a constant, as in the notebook.  `polyline_length`, `svg_length_loss` (:15-18) and `continuity_loss` (:10-12)
+complete the file; `emd_loss` is the batch loss and ``refine(loss="emd")`` the notebook's loop with the notebook's loss.
 """
 import torch
 from torch.autograd.function import once_differentiable
 
 from . import ops
 
-__all__ = ["sample_points", "chamfer", "reconstruction_error", "chamfer_loss", "refine"]
+__all__ = ["sample_points", "chamfer", "reconstruction_error", "chamfer_loss", "refine", "emd", "emd_loss", "polyline_length",
+           "svg_length_loss", "continuity_loss"]
 
 
 class _SamplePoints(torch.autograd.Function):
@@ -52,6 +62,37 @@ class _Chamfer(torch.autograd.Function):
     def backward(ctx, dout):
         dpx, dpy = ops.chamfer_bwd(*ctx.saved_tensors, dout.contiguous())
         return dpx if ctx.needs_input_grad[0] else None, None, dpy if ctx.needs_input_grad[2] else None, None
+
+
+class _Emd(torch.autograd.Function):
+    """ops.emd with ops.emd_bwd behind it; the gradient is for the pred cloud only"""
+
+    @staticmethod
+    def forward(ctx, px, nx, py, ny, first_point_weight):
+        out, shift, matched, t = ops.emd(px, nx, py, ny, first_point_weight)
+        ctx.save_for_backward(px, nx, ny, t, shift)
+        ctx.first_point_weight = first_point_weight
+        ctx.mark_non_differentiable(shift, matched)
+        return out, shift, matched
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout, _dshift, _dmatched):
+        return ops.emd_bwd(*ctx.saved_tensors, dout.contiguous(), ctx.first_point_weight), None, None, None, None
+
+
+class _PolylineLength(torch.autograd.Function):
+    """ops.polyline_length with ops.polyline_length_bwd behind it"""
+
+    @staticmethod
+    def forward(ctx, p, n):
+        ctx.save_for_backward(p, n)
+        return ops.polyline_length(p, n)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        return ops.polyline_length_bwd(*ctx.saved_tensors, dout.contiguous()), None
 
 
 def sample_points(commands, args, n=10):
@@ -119,18 +160,78 @@ def chamfer_loss(commands, args, target_points, target_counts, n=10):
     return {"loss": loss, "per_icon": per_icon, "valid": valid}
 
 
-def refine(commands, args, target_points, target_counts, steps=150, lr=0.1, n=10):
+def emd(points_x, counts_x, points_y, counts_y, first_point_weight=False, return_matched_indices=False):
+    """The reference's ``svg_emd_loss`` (deepsvg/difflib/loss.py:21-51) of pred clouds x against target clouds y, both as
+    sample_points returns them -> f32 [N]; with `return_matched_indices` -> (loss, matched int32 [N, cap_x], shift int32
+    [N]): matched[i, k] is the index into points_y[i] AS PASSED (the orientation flip is undone) of the point paired with
+    x_k, -1 past counts_x[i].  0 where x is empty, NaN where only y is.  `first_point_weight` counts the first pair 10
+    times; it does not influence the shift.  Differentiable with respect to points_x ONLY (the target is a constant, as in
+    the notebook); the same bits with and without gradients, bit-reproducible."""
+    clouds = (points_x.contiguous(), counts_x.contiguous(), points_y.detach().contiguous(), counts_y.contiguous())
+    if torch.is_grad_enabled() and points_x.requires_grad:
+        loss, shift, matched = _Emd.apply(*clouds, bool(first_point_weight))
+    else:
+        loss, shift, matched, _ = ops.emd(*clouds, bool(first_point_weight))
+    return (loss, matched, shift) if return_matched_indices else loss
+
+
+def emd_loss(commands, args, target_points, target_counts, n=10, first_point_weight=False):
+    """chamfer_loss with `emd` in the place of `chamfer`: -> {"loss": 0-d, "per_icon": f32 [N], "valid": bool [N]}, `valid`
+    where both clouds are non-empty, `loss` the mean of `per_icon` over the valid icons (NaN when there is none; the
+    gradient is zero on the others either way)."""
+    points, counts = sample_points(commands, args, n)
+    per_icon = emd(points, counts, target_points, target_counts, first_point_weight)
+    valid = (counts > 0) & (target_counts > 0)
+    loss = torch.where(valid, per_icon, torch.zeros_like(per_icon)).sum() / valid.sum()
+    return {"loss": loss, "per_icon": per_icon, "valid": valid}
+
+
+def polyline_length(points, counts):
+    """clouds as sample_points returns them -> f32 [N]: sum_i |p_{i+1} - p_i| over the points in use (``get_length``,
+    deepsvg/difflib/utils.py:67-69), 0 for clouds of 0 or 1 point.  Differentiable with respect to `points`; a zero-length
+    segment contributes no gradient."""
+    points, counts = points.contiguous(), counts.contiguous()
+    if torch.is_grad_enabled() and points.requires_grad:
+        return _PolylineLength.apply(points, counts)
+    return ops.polyline_length(points, counts)
+
+
+def svg_length_loss(points_x, counts_x, points_y, counts_y):
+    """The reference's ``svg_length_loss`` (loss.py:15-18): |L_y - L_x| / L_y -> f32 [N], NaN (and a zero gradient)
+    where L_y == 0.  Differentiable with respect to points_x; the target is a constant."""
+    target = polyline_length(points_y.detach(), counts_y)
+    ratio = (target - polyline_length(points_x, counts_x)).abs() / torch.where(target > 0, target, torch.ones_like(target))
+    return torch.where(target > 0, ratio, torch.full_like(ratio, float("nan")))
+
+
+def continuity_loss(points, counts):
+    """The reference's ``continuity_loss`` (loss.py:10-12): the mean segment length L / (count - 1) -> f32 [N], NaN where
+    count < 2 (the mean of nothing).  Differentiable with respect to `points`."""
+    segments = (counts - 1).clamp(min=0).to(torch.float32)
+    length = polyline_length(points, counts)
+    return torch.where(segments > 0, length / segments.clamp(min=1), torch.full_like(length, float("nan")))
+
+
+_REFINE_LOSSES = {"chamfer": chamfer_loss, "emd": emd_loss}
+
+
+def refine(commands, args, target_points, target_counts, steps=150, lr=0.1, n=10, loss="chamfer"):
     """The loop of notebooks/svgtensor.ipynb ("Differentiable SVGTensor optimization") for a whole batch: Adam on a float32
-    copy of `args`, minimising `chamfer_loss` against the target clouds.  -> (refined args f32, history f32 [steps]: the
+    copy of `args`, minimising `chamfer_loss` (loss="chamfer", the default) or `emd_loss` (loss="emd") against the target
+    clouds.  The notebook's own cell minimises ``svg_emd_loss``, i.e. loss="emd"; the order-free Chamfer distance also accepts
+    a curve that visits the right places in another order.  -> (refined args f32, history f32 [steps]: the
     loss before each step, kept on the device - the loop reads nothing back).  Elements whose gradient is always zero
     (columns 0-4, padding, rows that neither draw nor precede a drawing row) come back as they went in."""
+    if loss not in _REFINE_LOSSES:
+        raise ValueError(f"refine: loss {loss!r}, need one of {sorted(_REFINE_LOSSES)}")
+    batch_loss = _REFINE_LOSSES[loss]
     refined = args.detach().float().clone().requires_grad_(True)
     opt = torch.optim.Adam([refined], lr=lr)
     history = torch.empty(steps, dtype=torch.float32, device=refined.device)
     for step in range(steps):
         opt.zero_grad(set_to_none=True)
-        loss = chamfer_loss(commands, refined, target_points, target_counts, n)["loss"]
-        loss.backward()
-        history[step] = loss.detach()
+        value = batch_loss(commands, refined, target_points, target_counts, n)["loss"]
+        value.backward()
+        history[step] = value.detach()
         opt.step()
     return refined.detach(), history

@@ -1291,6 +1291,71 @@ def sample_points_bwd(commands, dpoints, n=10, groups=1):
     return dargs
 
 
+def emd(px, nx, py, ny, first_point_weight=False):
+    """the ordered point loss svg_emd_loss (difflib/loss.py:21-51) of pred clouds px / nx against target clouds py / ny ->
+    (out f32 [B], shift int32 [B], matched int32 [B, capx]: the index into py[b] as passed that px[b, k] is paired with, -1
+    past nx[b]; t f32 [B, capx, 2]: the matched target points before the shift, rows past nx[b] not written - emd_bwd's
+    input).  out is 0 where nx[b] == 0 and NaN where only ny[b] == 0"""
+    B, capx, capy = _chk_clouds(px, nx, py, ny)
+    L = _l.load()
+    out = torch.empty(B, dtype=torch.float32, device=px.device)
+    shift = torch.empty(B, dtype=torch.int32, device=px.device)
+    matched = torch.empty(B, capx, dtype=torch.int32, device=px.device)
+    t = torch.empty(B, capx, 2, dtype=torch.float32, device=px.device)
+    ws_bytes = L.dsvg_emd_workspace_bytes(B, capx)        # per-block minima of the shift search and the unshifted matching
+    ws = torch.empty(max(ws_bytes // 8 + 1, 1), dtype=torch.float64, device=px.device)
+    _l.check(L.dsvg_emd(px.data_ptr(), nx.data_ptr(), capx, py.data_ptr(), ny.data_ptr(), capy, B, int(bool(first_point_weight)),
+                        out.data_ptr(), shift.data_ptr(), matched.data_ptr(), t.data_ptr(), ws.data_ptr(), ws_bytes,
+                        _stream()), "dsvg_emd")
+    return out, shift, matched, t
+
+
+def emd_bwd(px, nx, ny, t, shift, dout, first_point_weight=False):
+    """the pred clouds, the target counts and emd's `t` and `shift`, dout f32 [B] -> dpx f32 [B, capx, 2]: every row written,
+    zeros past the counts and on icons with an empty cloud (whatever dout holds there); the target gets no gradient"""
+    _chk(px, nx, ny, t, shift, dout)
+    assert px.dtype == torch.float32 and px.dim() == 3 and px.shape[2] == 2 and px.is_contiguous()
+    B, capx = px.shape[0], px.shape[1]
+    assert nx.dtype == torch.int32 and nx.shape == (B,) and nx.is_contiguous()
+    assert ny.dtype == torch.int32 and ny.shape == (B,) and ny.is_contiguous()
+    assert t.dtype == torch.float32 and t.shape == (B, capx, 2) and t.is_contiguous()
+    assert shift.dtype == torch.int32 and shift.shape == (B,) and shift.is_contiguous()
+    assert dout.dtype == torch.float32 and dout.shape == (B,) and dout.is_contiguous()
+    dpx = torch.empty_like(px)
+    _l.check(_l.load().dsvg_emd_bwd(px.data_ptr(), nx.data_ptr(), capx, ny.data_ptr(), t.data_ptr(), shift.data_ptr(),
+                                    dout.data_ptr(), int(bool(first_point_weight)), B, dpx.data_ptr(), _stream()),
+             "dsvg_emd_bwd")
+    return dpx
+
+
+def _chk_cloud(p, n):
+    _chk(p, n)
+    assert p.dtype == torch.float32 and p.dim() == 3 and p.shape[2] == 2 and p.is_contiguous()
+    assert n.dtype == torch.int32 and n.shape == (p.shape[0],) and n.is_contiguous()
+    return p.shape[0], p.shape[1]
+
+
+def polyline_length(p, n):
+    """p f32 [B, cap, 2] with n int32 [B] points in use -> f32 [B]: sum_i |p_{i+1} - p_i| (difflib/utils.py:67-69), 0 for
+    clouds of 0 or 1 point"""
+    B, cap = _chk_cloud(p, n)
+    out = torch.empty(B, dtype=torch.float32, device=p.device)
+    _l.check(_l.load().dsvg_polyline_length(p.data_ptr(), n.data_ptr(), cap, B, out.data_ptr(), _stream()),
+             "dsvg_polyline_length")
+    return out
+
+
+def polyline_length_bwd(p, n, dout):
+    """the cloud of polyline_length, dout f32 [B] -> dp f32 [B, cap, 2]: every row written, zeros past the counts"""
+    B, cap = _chk_cloud(p, n)
+    _chk(dout)
+    assert dout.dtype == torch.float32 and dout.shape == (B,) and dout.is_contiguous()
+    dp = torch.empty_like(p)
+    _l.check(_l.load().dsvg_polyline_length_bwd(p.data_ptr(), n.data_ptr(), cap, B, dout.data_ptr(), dp.data_ptr(), _stream()),
+             "dsvg_polyline_length_bwd")
+    return dp
+
+
 # ------------------------------------------------------------------------------------------------
 # device-side batch assembly (svgtensor_dataset.py:164-205)
 # ------------------------------------------------------------------------------------------------

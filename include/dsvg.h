@@ -45,8 +45,10 @@ extern "C" {
  *     bwd, dsvg_attention_long_packed_fwd / bwd, dsvg_attention_long_mfma_fwd / bwd added.
  * 12: dsvg_ffn_bwd removed (the fully fused FFN backward: no caller since round 2; dsvg_ffn_bwd_dx is the FFN backward's kernel).
  * 13: dsvg_sample_points / dsvg_chamfer (+ dsvg_chamfer_workspace_bytes) added (reconstruction error of decoded icons, evaluation only); DSVG_I64.
- * 14: dsvg_chamfer_nn / dsvg_chamfer_bwd / dsvg_sample_points_bwd added (the gradient of the reconstruction error). */
-#define DSVG_ABI_VERSION 14
+ * 14: dsvg_chamfer_nn / dsvg_chamfer_bwd / dsvg_sample_points_bwd added (the gradient of the reconstruction error).
+ * 15: dsvg_emd (+ dsvg_emd_workspace_bytes) / dsvg_emd_bwd / dsvg_polyline_length / dsvg_polyline_length_bwd added (the ordered
+ *     point loss and the length losses of deepsvg/difflib/loss.py). */
+#define DSVG_ABI_VERSION 15
 
 const char* dsvg_last_error(void);
 int dsvg_version(void);
@@ -556,6 +558,44 @@ int dsvg_chamfer_bwd(const float* px, const int32_t* nx, int64_t capx, const flo
                      void* stream);
 int dsvg_sample_points_bwd(const float* commands, int64_t B, int32_t G, int32_t L, int32_t n, const float* dpoints,
                            float* dargs, void* stream);
+
+/* The ordered point loss svg_emd_loss (deepsvg/difflib/loss.py:21-51), the loss notebooks/svgtensor.ipynb minimises, and the
+ * polyline length behind svg_length_loss (:15-18) and continuity_loss (:10-12); clouds laid out as for dsvg_chamfer.  x is
+ * the pred cloud (n = nx[b] points), y the target (m = ny[b]); the target is a constant: gradients are for x only.
+ *  emd: (1) orientation (make_clockwise, utils.py:52-60): A = sum_{j<m-1} (y_j.x y_{j+1}.y - y_{j+1}.x y_j.y), the open
+ *    polyline, in float64; y is kept if A > 0 and read reversed otherwise (A == 0 and NaN reverse).  (2) arc-length
+ *    distribution (get_length_distribution, utils.py:72-81) of the oriented cloud y': D_0 = 0, D_j = (sum_{i<j} |y'_{i+1} -
+ *    y'_i|) / total, lengths and prefix sums in float64 (the reference's fp32 cumsum cannot resolve near matches); total ==
+ *    0 or m == 1: every point matches index 0 of y' (the reference divides by zero).  (3) matching (loss.py:32-36): u_i =
+ *    i / (n - 1) in float64 (u_0 = 0 when n == 1), match_i = argmin_j |u_i - D_j|, the lowest j of a tie; t_i = y'[match_i].
+ *    A binary search per pred point on chunks of 1,024 D values: no [n, m] matrix and nothing of size m is stored, so
+ *    capy is any size below 2^31.  (4) shift (loss.py:39-46): S(s) = sum_k |x_k - t_{(k+s) mod n}| for s = 0 .. n - 1, fp32
+ *    terms (one sqrtf each) added in float64 in ascending k; s* = the lowest s that attains the minimum (np.argmin); with
+ *    first_point_weight the term k = 0 of S(s*) counts 10 times - the weight does not influence s*, as in the reference.
+ *    out[b] = S(s*) / n fp32; shift[b] = s* int32; matched int32 [B, capx]: matched[b, k] = the index into y AS PASSED (not
+ *    into y') of the point paired with x_k, i.e. reorder(matching, s*) of return_matched_indices mapped back through the
+ *    reversal, -1 in rows past nx[b]; t fp32 [B, capx, 2]: t_i as gathered in (3), before the shift, rows past nx[b] not
+ *    written - what dsvg_emd_bwd needs.  n == 0: out 0 (loss.py:25-26); n > 0 and m == 0: out NaN (the reference raises);
+ *    both with shift 0 and matched -1.  capx <= 65536 (the shift search is quadratic in n; one workgroup per icon and 256
+ *    shifts).  workspace: dsvg_emd_workspace_bytes(B, capx) bytes, 8-byte aligned; it is dead once the call's work is done.
+ *    No atomics, fixed summation orders: bit-reproducible.  On integer coordinates every S(s) is exact, so two shifts
+ *    with the same terms tie exactly and the lower one is returned.
+ *  emd_bwd: dpx[b, k] = dout[b] w_k (x_k - t_{(k+s*) mod n}) / (|x_k - t_{(k+s*) mod n}| n) with w_0 = 10 under
+ *    first_point_weight and w_k = 1 otherwise; exactly 0 where the two points coincide.  dpx fp32 [B, capx, 2]: ALL rows
+ *    written, zeros past nx[b] and in every row of an icon with an empty cloud, whatever dout[b] holds.  Element-wise.
+ *  polyline_length: out[b] = sum_{i < n-1} |p_{i+1} - p_i| (get_length, utils.py:67-69) over the first n[b] points of p
+ *    [B, cap, 2], float64 inside in a fixed order, fp32 out; 0 for 0 or 1 point.  polyline_length_bwd: dp[b, i] = dout[b]
+ *    (u(p_i, p_{i-1}) - u(p_{i+1}, p_i)) with u(a, b) = (a - b) / |a - b|, 0 on a zero-length segment; all rows written,
+ *    zeros past n[b].  Both bit-reproducible. */
+int64_t dsvg_emd_workspace_bytes(int64_t B, int64_t capx);
+int dsvg_emd(const float* px, const int32_t* nx, int64_t capx, const float* py, const int32_t* ny, int64_t capy, int64_t B,
+             int32_t first_point_weight, float* out, int32_t* shift, int32_t* matched, float* t, void* workspace,
+             int64_t workspace_bytes, void* stream);
+int dsvg_emd_bwd(const float* px, const int32_t* nx, int64_t capx, const int32_t* ny, const float* t, const int32_t* shift,
+                 const float* dout, int32_t first_point_weight, int64_t B, float* dpx, void* stream);
+int dsvg_polyline_length(const float* p, const int32_t* n, int64_t cap, int64_t B, float* out, void* stream);
+int dsvg_polyline_length_bwd(const float* p, const int32_t* n, int64_t cap, int64_t B, const float* dout, float* dp,
+                             void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The argument head fused with its consumers (csrc/head_fused.hip): args_fcn = Linear(256 -> n_args *

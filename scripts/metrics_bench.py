@@ -10,6 +10,10 @@ of S + 2 = 32 tokens), n = 10 points per command:
   the backward legs   ops.chamfer_nn (next to ops.chamfer: the same sweep with the arg-min kept), ops.chamfer_bwd,
                       ops.sample_points_bwd, one step of metrics.refine's loop (sample_points -> chamfer -> backward -> Adam),
                       and the reference's way again: the per-icon torch.cdist loop with autograd through it
+  the ordered loss    (`typical` clouds only) ops.emd, ops.emd_bwd and one step of metrics.refine(loss="emd"), against a
+                      per-icon torch loop of the same definition (include/dsvg.h: float64 orientation and arc lengths,
+                      searchsorted matching, all n shifts of an icon at once from an [n, n] gather - kinder to torch than the
+                      reference's Python loop over the n shifts, deepsvg/difflib/loss.py:39), forward and with autograd
 
 HIP events around `inner` back-to-back calls, median of 20 such runs after warm-up.  The VALU floor quoted for the Chamfer
 launch is pairs * 4.5 vector instructions (2 subtractions, multiply, fused multiply-add, half a 3-way minimum: the kernel's inner
@@ -53,6 +57,31 @@ def chamfer_torch_loop(px, nx, py, ny):
     for b in range(px.shape[0]):
         d = torch.cdist(px[b, :nx[b]], py[b, :ny[b]])
         out.append(d.min(dim=0).values.mean() + d.min(dim=1).values.mean())
+    return torch.stack(out)
+
+
+def emd_torch_loop(px, nx, py, ny):
+    """the ordered loss of include/dsvg.h one icon at a time (counts on the host, both clouds non-empty)"""
+    out = []
+    for b in range(px.shape[0]):
+        n, m = nx[b], ny[b]
+        x, y = px[b, :n], py[b, :m].double()
+        if not bool((y[:-1, 0] * y[1:, 1] - y[1:, 0] * y[:-1, 1]).sum() > 0):
+            y = y.flip(0)
+        cum = torch.cat([y.new_zeros(1), (y[1:] - y[:-1]).norm(dim=-1).cumsum(0)])
+        if m == 1 or not bool(cum[-1] > 0):
+            j = torch.zeros(n, dtype=torch.long, device=px.device)
+        else:
+            D = cum / cum[-1]
+            u = torch.arange(n, dtype=torch.float64, device=px.device) / max(n - 1, 1)
+            hi = torch.searchsorted(D, u).clamp(max=m - 1)
+            lo = (hi - 1).clamp(min=0)
+            j = torch.where((u - D[lo]).abs() <= (D[hi] - u).abs(), lo, hi)
+        t = y[j].float()
+        k = torch.arange(n, device=px.device)
+        S = (x.unsqueeze(0) - t[(k.unsqueeze(0) + k.unsqueeze(1)) % n]).norm(dim=-1).sum(1)          # [shift, point]
+        s = int(S.argmin())
+        out.append((x - torch.cat([t[s:], t[:s]])).norm(dim=-1).mean())
     return torch.stack(out)
 
 
@@ -145,6 +174,36 @@ def main():
         print(f"[{tag}] torch.cdist loop, forward + autograd backward (5 runs): {med_tb:8.2f} ms [{lo_t:.2f} .. {hi_t:.2f}] = "
               f"{med_tb / (med_nn + med_b):.0f} x chamfer_nn + chamfer_bwd; max |kernel - fp32 cdist autograd| on d / d points "
               f"{float(diff.max()):.2e}, above 1e-5 in {int((diff > 1e-5).sum())} of {int(live.sum()) * 2} entries")
+        if tag != "typical":
+            continue
+        # ---- the ordered loss ----
+        terms = int((nx.long() * nx.long()).sum())
+        med_e, lo, hi = timed(lambda: ops.emd(px, nx, py, ny), inner=5)
+        print(f"[{tag}] emd: {med_e * 1e3:8.1f} us [{lo * 1e3:.1f} .. {hi * 1e3:.1f}] = {med_e / med:.2f} x chamfer; {terms / 1e9:.2f} G "
+              f"shift terms, {terms / med_e / 1e9:.1f} T terms/s")
+        out_e, shift, _, t = ops.emd(px, nx, py, ny)
+        med_eb, lo, hi = timed(lambda: ops.emd_bwd(px, nx, ny, t, shift, dout), inner=20)
+        print(f"[{tag}] emd_bwd: {med_eb * 1e3:8.1f} us [{lo * 1e3:.1f} .. {hi * 1e3:.1f}]")
+
+        def refine_step_emd():
+            opt.zero_grad(set_to_none=True)
+            metrics.emd_loss(ca, ref, py, ny, NPTS)["loss"].backward()
+            opt.step()
+        med_re, lo, hi = timed(refine_step_emd, inner=5)
+        print(f"[{tag}] one refine(loss='emd') step (sample_points, emd, emd_bwd, sample_points_bwd, masked mean, Adam): "
+              f"{med_re * 1e3:8.1f} us [{lo * 1e3:.1f} .. {hi * 1e3:.1f}] = {med_re / med_r:.2f} x the Chamfer step")
+        want_e = emd_torch_loop(px, nxl, py, nyl)
+        med_te, lo_t, hi_t = timed(lambda: emd_torch_loop(px, nxl, py, nyl), inner=1, runs=3, warmup=1)
+        print(f"[{tag}] torch loop of the ordered loss over {N} icons (3 runs): {med_te:8.2f} ms [{lo_t:.2f} .. {hi_t:.2f}] = "
+              f"{med_te / med_e:.0f} x the kernel; max |kernel - torch loop| {float((out_e - want_e).abs().max()):.2e}, mean loss "
+              f"{float(out_e.mean()):.4f}")
+
+        def emd_loop_backward():
+            pxl.grad = None
+            emd_torch_loop(pxl, nxl, py, nyl).sum().backward()
+        med_teb, lo_t, hi_t = timed(emd_loop_backward, inner=1, runs=3, warmup=1)
+        print(f"[{tag}] torch loop of the ordered loss, forward + autograd backward (3 runs): {med_teb:8.2f} ms [{lo_t:.2f} .. "
+              f"{hi_t:.2f}] = {med_teb / (med_e + med_eb):.0f} x emd + emd_bwd")
 
 
 if __name__ == "__main__":
