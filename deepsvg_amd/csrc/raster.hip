@@ -1,0 +1,310 @@
+// Images of a decoded batch: the curves sample_points draws (SVGTensor.sample_points, deepsvg/difflib/tensor.py:191-230),
+// rasterised into anti-aliased coverage images, as outlines or filled - what the reference gets one icon at a time from
+// SVG.draw -> cairosvg on the host (deepsvg/svglib/svg.py:172-204; fill without stroke: svglib/svg_primitive.py:34-38).
+// The definition of an image is in include/dsvg.h; tests/raster_ref.py restates it in float64.
+//   dsvg_raster_segments  one workgroup per image (the G sequences of an icon, in group order): ballots + prefix sums give
+//                         every drawing command, and in fill mode every sub-path's closing chord, its offset
+//                         (block_flag_scan of flag_scan.h, as dsvg_sample_points); the (command, chord) pairs are then
+//                         evaluated by consecutive lanes.  Vertex 0 of a command is its start point and vertex n - 1 its end
+//                         position bit for bit, so consecutive chords share their vertices exactly.
+//   dsvg_raster_sweep     one workgroup per (image, tile of 32 x 32 pixels): a wave owns a 16 x 16 quadrant, a lane four
+//                         pixels of one column, 4 rows apart, in registers; the image's chords stream through LDS in tiles
+//                         (every lane reads the same address: a broadcast); running minimum of the SQUARED distance, one sqrt
+//                         per pixel after the sweep; in fill mode a running winding count per pixel, folded into an
+//                         `inside` bit at every sequence start.  No atomics, no scratch: bit-reproducible.
+#include "dsvg_common.h"
+#include "flag_scan.h"
+#include "../../include/dsvg.h"
+
+namespace {
+constexpr int RS_N_ARGS = 11;
+constexpr int RS_CMD_L = 1, RS_CMD_C = 2;
+constexpr int RS_REC = 5;                 // words of a chord record: ax, ay, bx - ax, by - ay, flags
+constexpr int RS_THREADS = 256;
+constexpr int RS_TILE = 32;               // pixels per side of a workgroup's tile
+constexpr int RS_QUAD = 16;               // pixels per side of a wave's quadrant
+constexpr int RS_PIX = 4;                 // pixels of a lane: rows ly, ly + 4, ly + 8, ly + 12 of its quadrant
+constexpr int RS_CHORDS = 512;            // chords per LDS tile (16 KiB of records, 8 KiB of boxes when culling)
+constexpr int RS_MAX_SIZE = 4096;
+
+// chords an image can hold: n - 1 per token, and in fill mode one closing chord per sub-path (two sub-paths of a sequence
+// have a non-drawing row between them: at most (L + 1) / 2 of them)
+inline int64_t raster_cap(int64_t G, int64_t L, int64_t n, int fill) {
+    return G * (L * (n - 1) + (fill ? (L + 1) / 2 : 0));
+}
+
+// flags word of a record: bit 0 = the first chord of a sequence; bits 1..31 = on a closing chord, how many records back
+// its sub-path's first chord lies (>= n - 1 >= 1), 0 on every other chord
+template <typename T>
+__global__ __launch_bounds__(SP_THREADS) void raster_segments_kernel(const T* __restrict__ commands, const T* __restrict__ args,
+                                                                     int G, int L, int n, int fill, long long cap,
+                                                                     float* __restrict__ segs, int32_t* __restrict__ seg_counts) {
+    __shared__ int pre[SP_MAX_TOK + 1];       // drawing commands of the image before token t
+    __shared__ int cl[SP_MAX_TOK + 1];        // sub-paths that end before token t (fill mode; all zero otherwise)
+    __shared__ int src[SP_MAX_TOK];           // token of the j-th drawing command
+    __shared__ int first[SP_MAX_TOK];         // first token of the q-th sub-path
+    __shared__ int wtot[SP_MAX_TOK / 64];
+    const long long b = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int T_ = G * L;
+    const T* cmd = commands + b * T_;
+    const T* arg = args + b * T_ * RS_N_ARGS;
+
+    // ---- pass 1: where every command's chords and every sub-path's closing chord go --------------------------------------
+    block_flag_scan(T_, pre, wtot, [&](int t) {
+        if (t >= T_) return false;
+        const int c = (int)cmd[t];
+        return c == RS_CMD_L || c == RS_CMD_C;
+    });
+    // a sub-path ends at a drawing token that is the last row of its sequence or has a non-drawing row after it
+    block_flag_scan(T_, cl, wtot, [&](int t) {
+        if (!fill || t >= T_ || pre[t + 1] == pre[t]) return false;
+        return t % L == L - 1 || pre[t + 2] == pre[t + 1];
+    });
+    for (int t = tid; t < T_; t += SP_THREADS)
+        if (pre[t + 1] > pre[t]) {
+            src[pre[t]] = t;
+            if (fill && (t % L == 0 || pre[t] == pre[t - 1])) first[cl[t]] = t;      // cl[t] sub-paths lie before this one
+        }
+    __syncthreads();
+    const int K = pre[T_];
+    if (tid == 0) seg_counts[b] = K * (n - 1) + cl[T_];
+
+    float* out = segs + b * cap * RS_REC;
+    auto put = [&](long long o, float ax, float ay, float bx, float by, int flags) {
+        float* r = out + o * RS_REC;
+        r[0] = ax; r[1] = ay; r[2] = bx - ax; r[3] = by - ay; r[4] = __int_as_float(flags);
+    };
+    // start point of token t: the end position of the row before, whatever that row holds; (0, 0) on row 0 (tensor.py:75-82)
+    auto start_of = [&](int t) {
+        const T* a = arg + (long long)t * RS_N_ARGS;
+        return t % L ? make_float2((float)a[9 - RS_N_ARGS], (float)a[10 - RS_N_ARGS]) : make_float2(0.f, 0.f);
+    };
+
+    // ---- pass 2: work item (j, k) = chord k (vertex k -> vertex k + 1) of the j-th drawing command ----------------------------
+    const float nm1 = (float)(n - 1);
+    for (int w = tid; w < K * (n - 1); w += SP_THREADS) {
+        const int j = w / (n - 1), k = w - j * (n - 1);
+        const int t = src[j];
+        const int g = t / L;
+        const T* a = arg + (long long)t * RS_N_ARGS;
+        const float2 p0 = start_of(t);
+        const float p3x = (float)a[9], p3y = (float)a[10];
+        const bool cubic = (int)cmd[t] == RS_CMD_C;
+        float c1x = 0.f, c1y = 0.f, c2x = 0.f, c2y = 0.f, c3x = 0.f, c3y = 0.f;
+        if (cubic) {
+            const float p1x = (float)a[5], p1y = (float)a[6], p2x = (float)a[7], p2y = (float)a[8];
+            // power basis of the cubic Bezier (exact for integer arguments), as sample_points_kernel
+            c1x = 3.f * (p1x - p0.x); c2x = 3.f * (p0.x - 2.f * p1x + p2x); c3x = (p3x - p0.x) + 3.f * (p1x - p2x);
+            c1y = 3.f * (p1y - p0.y); c2y = 3.f * (p0.y - 2.f * p1y + p2y); c3y = (p3y - p0.y) + 3.f * (p1y - p2y);
+        }
+        // vertex q: the start point and the end position themselves at q = 0 and q = n - 1; between them Horner in z =
+        // q / (n - 1) for `c`, and ((n - 1 - q) p0 + q p3) / (n - 1) for `l` (an exact numerator for integer arguments)
+        float2 v[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int q = k + e;
+            const float fq = (float)q;
+            if (q == 0) v[e] = p0;
+            else if (q == n - 1) v[e] = make_float2(p3x, p3y);
+            else if (cubic) {
+                const float z = fq / nm1;
+                v[e] = make_float2(fmaf(fmaf(fmaf(c3x, z, c2x), z, c1x), z, p0.x), fmaf(fmaf(fmaf(c3y, z, c2y), z, c1y), z, p0.y));
+            } else {
+                const float fr = (float)(n - 1 - q);
+                v[e] = make_float2(fmaf(fq, p3x, fr * p0.x) / nm1, fmaf(fq, p3y, fr * p0.y) / nm1);
+            }
+        }
+        put((long long)j * (n - 1) + cl[t] + k, v[0].x, v[0].y, v[1].x, v[1].y, k == 0 && j == pre[g * L] ? 1 : 0);
+    }
+    // ---- pass 3 (fill): the closing chord of every sub-path, from its last vertex to its first, behind its last chord ----------
+    if (fill)
+        for (int t = tid; t < T_; t += SP_THREADS)
+            if (cl[t + 1] > cl[t]) {
+                const int tf = first[cl[t]];
+                const T* a = arg + (long long)t * RS_N_ARGS;
+                const float2 p = start_of(tf);
+                put((long long)(pre[t] + 1) * (n - 1) + cl[t], (float)a[9], (float)a[10], p.x, p.y,
+                    ((pre[t] + 1 - pre[tf]) * (n - 1)) << 1);
+            }
+}
+
+// Workgroup (image b, tile row ty, tile column tx).  LDS record of a chord: (ax, ay, dx, dy), (1 / |d|^2 or 0, by, flags, -)
+// with by the y of the chord's end vertex AS THE NEXT CHORD HOLDS IT (the record after it; on a closing chord its sub-path's
+// first record): ay + dy is that value only up to rounding, and the half-open crossing rule is watertight only when a
+// shared vertex is one number.  With CULL a wave skips the distance work of a chord whose bounding box is farther from the
+// wave's 16 x 16 pixel centres than the distance at which ink saturates (plus a margin far above the rounding of either
+// side); such a chord cannot change a pixel.  The crossing test is never skipped.
+template <bool FILL, bool CULL>
+__global__ __launch_bounds__(RS_THREADS) void raster_sweep_kernel(const float* __restrict__ segs, const int32_t* __restrict__ seg_counts,
+                                                                  long long cap, int size, int tiles, float s, float half_w,
+                                                                  float* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float4 rec[RS_CHORDS * 2];
+    __shared__ __attribute__((aligned(16))) float4 box[CULL ? RS_CHORDS : 1];
+    const long long blk = blockIdx.x;
+    const int tx = (int)(blk % tiles), ty = (int)((blk / tiles) % tiles);
+    const long long b = blk / ((long long)tiles * tiles);
+    const int cnt = (int)min((long long)max(seg_counts[b], 0), cap);
+    const float* sg = segs + b * cap * RS_REC;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int col0 = tx * RS_TILE + (wave & 1) * RS_QUAD, row0 = ty * RS_TILE + (wave >> 1) * RS_QUAD;
+    const int col = col0 + (lane & 15), row = row0 + (lane >> 4);
+    const float cx = ((float)col + 0.5f) * s;
+    float cy[RS_PIX], m[RS_PIX];
+    int wind[RS_PIX], inside[RS_PIX];
+#pragma unroll
+    for (int r = 0; r < RS_PIX; ++r) {
+        cy[r] = ((float)(row + 4 * r) + 0.5f) * s;
+        m[r] = INFINITY;
+        wind[r] = 0;
+        inside[r] = 0;
+    }
+    // the wave's pixel centres span [qx0, qx1] x [qy0, qy1]
+    const float qx0 = ((float)col0 + 0.5f) * s, qx1 = ((float)(col0 + RS_QUAD - 1) + 0.5f) * s;
+    const float qy0 = ((float)row0 + 0.5f) * s, qy1 = ((float)(row0 + RS_QUAD - 1) + 0.5f) * s;
+    const float reach = (FILL ? 0.5f * s : half_w + 0.5f * s) * 1.001f + 0.01f;
+    const float reach2 = reach * reach;
+
+    for (int j0 = 0; j0 < cnt; j0 += RS_CHORDS) {
+        if (j0) __syncthreads();                       // the tile of the step before has been read
+#pragma unroll
+        for (int h = 0; h < RS_CHORDS / RS_THREADS; ++h) {
+            const int jl = h * RS_THREADS + tid, j = j0 + jl;
+            if (j < cnt) {
+                const float* r = sg + (long long)j * RS_REC;
+                const float ax = r[0], ay = r[1], dx = r[2], dy = r[3];
+                const int fl = __float_as_int(r[4]);
+                const float len2 = fmaf(dx, dx, dy * dy);
+                float by = ay + dy;
+                if (FILL) {       // records that break the rule of include/dsvg.h keep ay + dy: in bounds, not watertight
+                    const int back = (int)((unsigned)fl >> 1);
+                    if (back > 0 && back <= j) by = sg[(long long)(j - back) * RS_REC + 1];
+                    else if (back == 0 && j + 1 < cnt) by = sg[(long long)(j + 1) * RS_REC + 1];
+                }
+                rec[2 * jl] = make_float4(ax, ay, dx, dy);
+                rec[2 * jl + 1] = make_float4(len2 > 1e-30f ? 1.f / len2 : 0.f, by, __int_as_float(fl), 0.f);
+                if (CULL) box[jl] = make_float4(fminf(ax, ax + dx), fminf(ay, ay + dy), fmaxf(ax, ax + dx), fmaxf(ay, ay + dy));
+            }
+        }
+        __syncthreads();
+        const int c = min(RS_CHORDS, cnt - j0);
+        // one chord against the lane's four pixels; `near` is wave-uniform
+        auto chord = [&](int jl, bool near) {
+            const float4 A = rec[2 * jl], B = rec[2 * jl + 1];        // the same address in every lane
+            if (FILL && (__builtin_amdgcn_readfirstlane(__float_as_int(B.z)) & 1)) {
+#pragma unroll
+                for (int r = 0; r < RS_PIX; ++r) {
+                    inside[r] |= wind[r] != 0;
+                    wind[r] = 0;
+                }
+            }
+            const float px = cx - A.x;
+#pragma unroll
+            for (int r = 0; r < RS_PIX; ++r) {
+                const float py = cy[r] - A.y;
+                if (FILL) {
+                    // the crossing of the chord's line with the pixel's row lies at x > cx: e > 0 going down the image
+                    // (ay <= cy < by), e < 0 going up
+                    const float e = fmaf(A.z, py, -(A.w * px));
+                    wind[r] += (int)(A.y <= cy[r] && cy[r] < B.y && e > 0.f) - (int)(B.y <= cy[r] && cy[r] < A.y && e < 0.f);
+                }
+                if (near) {
+                    const float t = fminf(fmaxf(fmaf(px, A.z, py * A.w) * B.x, 0.f), 1.f);
+                    const float qx = fmaf(-t, A.z, px), qy = fmaf(-t, A.w, py);
+                    m[r] = fminf(m[r], fmaf(qx, qx, qy * qy));
+                }
+            }
+        };
+        if (!CULL) {
+            for (int jl = 0; jl < c; ++jl) chord(jl, true);
+        } else {
+            // 64 chords at a time: lane l tests the box of chord base + l against the wave's pixels, the ballot is the list
+            // of chords within reach.  Stroke mode visits those only; fill mode visits every chord for its crossings
+            for (int base = 0; base < c; base += 64) {
+                bool within = false;
+                if (base + lane < c) {
+                    const float4 bb = box[base + lane];
+                    const float gx = fmaxf(fmaxf(bb.x - qx1, qx0 - bb.z), 0.f), gy = fmaxf(fmaxf(bb.y - qy1, qy0 - bb.w), 0.f);
+                    within = !(fmaf(gx, gx, gy * gy) > reach2);
+                }
+                unsigned long long mask = __ballot(within);
+                if (FILL) {
+                    const int end = min(base + 64, c);
+                    for (int jl = base; jl < end; ++jl) chord(jl, (mask >> (jl - base)) & 1ull);
+                } else {
+                    while (mask) {
+                        chord(base + __ffsll((long long)mask) - 1, true);
+                        mask &= mask - 1ull;
+                    }
+                }
+            }
+        }
+    }
+    if (col >= size) return;
+#pragma unroll
+    for (int r = 0; r < RS_PIX; ++r) {
+        if (row + 4 * r >= size) continue;
+        const float d = sqrtf(m[r]);
+        float ink;
+        if (FILL) ink = (inside[r] | (wind[r] != 0)) ? 0.5f + d / s : 0.5f - d / s;
+        else ink = 0.5f + (half_w - d) / s;
+        out[(b * size + (row + 4 * r)) * size + col] = fminf(fmaxf(ink, 0.f), 1.f);
+    }
+}
+}  // namespace
+
+extern "C" int64_t dsvg_raster_workspace_bytes(int64_t n_images, int32_t G, int32_t L, int32_t n, int32_t fill) {
+    if (n_images <= 0 || G < 1 || L < 1 || n < 2) return 0;
+    return n_images * raster_cap(G, L, n, fill) * RS_REC * (int64_t)sizeof(float);
+}
+
+extern "C" int dsvg_raster_segments(int32_t itype, const void* commands, const void* args, int64_t B, int32_t G, int32_t L,
+                                    int32_t n, int32_t fill, void* segs, int64_t segs_bytes, int32_t* seg_counts, void* stream) {
+    DSVG_CHECK_ARG(commands && args && segs && seg_counts, "raster_segments: null pointer");
+    DSVG_CHECK_ARG(itype == DSVG_F32 || itype == DSVG_I64, "raster_segments: itype %d is neither DSVG_F32 nor DSVG_I64", itype);
+    DSVG_CHECK_ARG(n >= 2 && n <= 64, "raster_segments: n = %d points per command, need 2..64", n);
+    DSVG_CHECK_ARG(B > 0 && B < (1ll << 31) && G >= 1 && L >= 1 && (int64_t)G * L <= SP_MAX_TOK,
+                   "raster_segments: bad shape (B=%lld G=%d L=%d; G * L <= %d tokens per image)", (long long)B, G, L, SP_MAX_TOK);
+    const int64_t cap = raster_cap(G, L, n, fill);      // <= 2048 * 64: far below 2^31
+    DSVG_CHECK_ARG(segs_bytes >= dsvg_raster_workspace_bytes(B, G, L, n, fill) && ((uintptr_t)segs & 3) == 0,
+                   "raster_segments: buffer of %lld bytes, need %lld (4-byte aligned)", (long long)segs_bytes,
+                   (long long)dsvg_raster_workspace_bytes(B, G, L, n, fill));
+    hipStream_t st = (hipStream_t)stream;
+    if (itype == DSVG_I64)
+        hipLaunchKernelGGL(raster_segments_kernel<long long>, dim3((unsigned)B), dim3(SP_THREADS), 0, st,
+                           (const long long*)commands, (const long long*)args, G, L, n, fill ? 1 : 0, (long long)cap,
+                           (float*)segs, seg_counts);
+    else
+        hipLaunchKernelGGL(raster_segments_kernel<float>, dim3((unsigned)B), dim3(SP_THREADS), 0, st, (const float*)commands,
+                           (const float*)args, G, L, n, fill ? 1 : 0, (long long)cap, (float*)segs, seg_counts);
+    DSVG_LAUNCH_CHECK("raster_segments");
+    return 0;
+}
+
+extern "C" int dsvg_raster_sweep(const void* segs, const int32_t* seg_counts, int64_t B, int64_t cap, int32_t size,
+                                 float stroke_width, int32_t flags, float* out, void* stream) {
+    DSVG_CHECK_ARG(size >= 1 && size <= RS_MAX_SIZE, "raster_sweep: size = %d pixels per side, need 1..%d", size, RS_MAX_SIZE);
+    DSVG_CHECK_ARG(segs && seg_counts && out, "raster_sweep: null pointer");
+    DSVG_CHECK_ARG(stroke_width >= 0.f && stroke_width < 1e6f, "raster_sweep: stroke_width %g, need a finite width >= 0",
+                   (double)stroke_width);
+    DSVG_CHECK_ARG((flags & ~(DSVG_RASTER_FILL | DSVG_RASTER_CULL)) == 0, "raster_sweep: unknown flags 0x%x", flags);
+    const int64_t tiles = (size + RS_TILE - 1) / RS_TILE;
+    DSVG_CHECK_ARG(B > 0 && cap > 0 && cap < (1ll << 26) && B * tiles * tiles < (1ll << 31),
+                   "raster_sweep: bad shape (B=%lld cap=%lld: %lld workgroups; chords per image below 2^26, workgroups below "
+                   "2^31)", (long long)B, (long long)cap, (long long)(B * tiles * tiles));
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)(B * tiles * tiles)), block(RS_THREADS);
+    const float s = 256.f / (float)size, half_w = 0.5f * stroke_width;
+    const float* sg = (const float*)segs;
+    const bool fill = flags & DSVG_RASTER_FILL, cull = flags & DSVG_RASTER_CULL;
+#define RS_LAUNCH(F, C)                                                                                                  \
+    hipLaunchKernelGGL((raster_sweep_kernel<F, C>), grid, block, 0, st, sg, seg_counts, (long long)cap, size, (int)tiles, s, \
+                       half_w, out)
+    if (fill && cull) RS_LAUNCH(true, true);
+    else if (fill) RS_LAUNCH(true, false);
+    else if (cull) RS_LAUNCH(false, true);
+    else RS_LAUNCH(false, false);
+#undef RS_LAUNCH
+    DSVG_LAUNCH_CHECK("raster_sweep");
+    return 0;
+}

@@ -1357,6 +1357,54 @@ def polyline_length_bwd(p, n, dout):
 
 
 # ------------------------------------------------------------------------------------------------
+# images of a decoded batch (svglib/svg.py:172-204 on the curves of difflib/tensor.py:191-230; csrc/raster.hip)
+# ------------------------------------------------------------------------------------------------
+RASTER_CULL = True      # the default of raster_sweep's `cull`: faster on every configuration of profiles/raster_bench.log, same bits
+
+
+def raster_segments(commands, args, n=10, groups=1, fill=False):
+    """commands [B*groups, L] / args [B*groups, L, 11] as sample_points takes them -> (segs f32 [B, cap, 5], seg_counts int32
+    [B]): the chords of image b in drawing order, n - 1 per `l` / `c` command and, with `fill`, one closing chord behind
+    every sub-path; cap = groups * (L * (n - 1) + (L + 1) // 2 if fill else L * (n - 1)).  A record is ax, ay, bx - ax,
+    by - ay and a flags word (view it as int32; bit 0: the first chord of a sequence; bits 1..: on a closing chord the number of
+    records back to its sub-path's first chord).  Records past seg_counts[b] are not written"""
+    _chk(commands, args)
+    assert commands.dim() == 2 and args.dim() == 3 and args.shape[:2] == commands.shape and args.shape[2] == 11
+    assert commands.dtype == args.dtype and commands.dtype in (torch.float32, torch.int64)
+    assert commands.is_contiguous() and args.is_contiguous()
+    assert groups >= 1 and commands.shape[0] % groups == 0 and commands.shape[0] >= groups
+    B, L = commands.shape[0] // groups, commands.shape[1]
+    lib = _l.load()
+    cap = lib.dsvg_raster_workspace_bytes(B, groups, L, int(n), int(bool(fill))) // (20 * B)      # (0 for an n the call refuses)
+    segs = torch.empty(B, max(cap, 1), 5, dtype=torch.float32, device=commands.device)
+    seg_counts = torch.empty(B, dtype=torch.int32, device=commands.device)
+    _l.check(lib.dsvg_raster_segments(F32 if commands.dtype == torch.float32 else _l.DSVG_I64, commands.data_ptr(),
+                                      args.data_ptr(), B, groups, L, int(n), int(bool(fill)), segs.data_ptr(),
+                                      segs.numel() * 4, seg_counts.data_ptr(), _stream()), "dsvg_raster_segments")
+    return segs, seg_counts
+
+
+def raster_sweep(segs, seg_counts, size=64, stroke_width=3.2, fill=False, cull=None):
+    """the records of raster_segments (built with the same `fill`) -> f32 [B, size, size], 1 = ink: stroke or fill coverage as
+    include/dsvg.h defines it.  `cull` (None: RASTER_CULL) skips chords out of a wave's reach; the image has the same bits"""
+    _chk(segs, seg_counts)
+    assert segs.dtype == torch.float32 and segs.dim() == 3 and segs.shape[2] == 5 and segs.is_contiguous()
+    assert seg_counts.dtype == torch.int32 and seg_counts.shape == (segs.shape[0],) and seg_counts.is_contiguous()
+    B, cap = segs.shape[0], segs.shape[1]
+    flags = (_l.DSVG_RASTER_FILL if fill else 0) | (_l.DSVG_RASTER_CULL if (RASTER_CULL if cull is None else cull) else 0)
+    out = torch.empty(B, int(size), int(size), dtype=torch.float32, device=segs.device)
+    _l.check(_l.load().dsvg_raster_sweep(segs.data_ptr(), seg_counts.data_ptr(), B, cap, int(size), float(stroke_width),
+                                         flags, out.data_ptr(), _stream()), "dsvg_raster_sweep")
+    return out
+
+
+def rasterize(commands, args, size=64, stroke_width=3.2, fill=False, n=10, groups=1, cull=None):
+    """raster_segments -> raster_sweep: two launches for the whole batch -> f32 [B, size, size]"""
+    segs, seg_counts = raster_segments(commands, args, n=n, groups=groups, fill=fill)
+    return raster_sweep(segs, seg_counts, size=size, stroke_width=stroke_width, fill=fill, cull=cull)
+
+
+# ------------------------------------------------------------------------------------------------
 # device-side batch assembly (svgtensor_dataset.py:164-205)
 # ------------------------------------------------------------------------------------------------
 def assemble_batch(rows, slot_off, variant, G, L, grouped, want_args=True, want_rel=False, pad_val=-1.0,

@@ -1,0 +1,100 @@
+"""Images of a decoded batch, on the device: the step from command sequences to pictures.  Every use the reference makes of
+a trained model ends in ``SVG.from_tensor(...).draw(return_png=True)`` (deepsvg/svglib/svg.py:172-204): an SVG string handed to
+cairosvg on the host, one icon at a time after a device -> host copy (``decode()`` of notebooks/interpolation.ipynb,
+latent_ops.ipynb, animation.ipynb, fonts.ipynb; the trainer's visualisation hook, configs/deepsvg/default_icons.py:76-77).
+Here the curves `metrics.sample_points` samples are rasterised by two launches of csrc/raster.hip for the whole batch.
+
+What an image is (include/dsvg.h has the full definition, tests/raster_ref.py restates it in float64): `l` and `c` commands
+become n - 1 chords each; the view box is 0..256 argument units (``Bbox(256)``), pixel (row r, column c) has its centre at
+((c + 0.5) s, (r + 0.5) s) with s = 256 / size, y down.  Stroke mode (the reference's default): ink = clamp(0.5 +
+(stroke_width / 2 - d) / s, 0, 1) with d the distance to the nearest chord.  Fill mode (no stroke, as
+svglib/svg_primitive.py:34-38): every sub-path is closed, a pixel is inside an image when its non-zero winding number with
+respect to any ONE sequence's chords is not 0, and ink = clamp(0.5 +- d / s, 0, 1).  No atomics: bit-reproducible.  No
+gradient: a differentiable rasteriser is a separate piece of work.  The reference's per-path `filling` values, colours and
+the visualisation extras of ``draw`` are not drawn; arcs are not either (the reference's own sampler skips them).
+"""
+import torch
+
+from . import ops
+
+__all__ = ["rasterize", "reconstruction_images", "interpolate", "interpolation_alphas"]
+
+
+def rasterize(commands, args, size=64, stroke_width=3.2, fill=False, n=10):
+    """commands [N, S] -> one image per row; commands [N, G, S] -> one image per icon, all its groups drawn; args [..., S, 11].
+    float32 (as the dataset delivers them) and int64 (as greedy_sample returns them) are read as they are.
+    -> f32 [N, size, size], 1 = ink, 0 = paper.  `stroke_width` is in argument units (3.2 of 256 = the reference's .3 of a
+    24-unit view box); `fill` draws filled shapes without a stroke; `n` points per command, as sample_points.  Inputs are
+    detached: no gradient.
+
+    One image per group (the layers ``draw_colored`` gives random colours) comes from flattening the groups; composing them
+    is one line of torch::
+
+        layers = rasterize(commands.reshape(N * G, S), args.reshape(N * G, S, 11), fill=True).view(N, G, 1, size, size)
+        rgb = 1 - (layers * (1 - torch.rand(N, G, 3, 1, 1, device=layers.device))).amax(1)          # [N, 3, size, size]
+    """
+    if commands.dim() not in (2, 3) or args.dim() != commands.dim() + 1 or args.shape[:-1] != commands.shape:
+        raise ValueError(f"rasterize: commands (N, S) or (N, G, S) with args (..., S, 11); got {tuple(commands.shape)} "
+                         f"and {tuple(args.shape)}")
+    commands, args = commands.detach(), args.detach()
+    if commands.dtype != args.dtype or commands.dtype not in (torch.float32, torch.int64):
+        commands, args = commands.float(), args.float()
+    groups = commands.shape[1] if commands.dim() == 3 else 1
+    S = commands.shape[-1]
+    commands, args = commands.reshape(-1, S).contiguous(), args.reshape(-1, S, args.shape[-1]).contiguous()
+    return ops.rasterize(commands, args, size=size, stroke_width=stroke_width, fill=fill, n=n, groups=groups)
+
+
+def reconstruction_images(model, commands, args, label=None, size=64, temperature=0.0, **raster):
+    """Decode `commands` / `args` with ``model.greedy_sample`` (as `metrics.reconstruction_error` does: eval mode, no
+    gradients, ``concat_groups=False``) and draw the decoded icons next to the targets, taken exactly as passed.
+    -> {"decoded": f32 [N, size, size], "target": f32 [N, size, size]}.  `raster`: stroke_width, fill, n of `rasterize`.
+    The model's train / eval state is restored."""
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            commands_y, args_y = model.greedy_sample(commands, args, commands, args, label=label, concat_groups=False,
+                                                     temperature=temperature)
+            decoded = rasterize(commands_y, args_y, size=size, **raster)
+            target = rasterize(commands, args, size=size, **raster)
+    finally:
+        model.train(was_training)
+    return {"decoded": decoded, "target": target}
+
+
+def interpolation_alphas(steps, ease=True, device=None):
+    """linspace(0, 1, steps), through the notebooks' ease-in-out t^2 / (2 (t^2 - t) + 1) when `ease` is set -> f32 [steps]"""
+    t = torch.linspace(0, 1, steps, device=device)
+    return t * t / (2 * (t * t - t) + 1) if ease else t
+
+
+def interpolate(model, z1, z2, steps=25, ease=True, label=None, size=64, temperature=0.0, **raster):
+    """The interpolation loop of the notebooks (``interpolate`` / ``decode`` of notebooks/interpolation.ipynb) for a whole
+    batch: z = (1 - a) z1 + a z2 for the `steps` values a of `interpolation_alphas`, ONE ``greedy_sample(z=...)`` call over
+    all N * steps latents, one `rasterize`.  z1 / z2: the latents of N icons in either layout the model hands out, batch-first
+    (N, 1, 1, dim_z) or the seq-first (1, 1, N, dim_z) of ``encode_mode=True``.  `label` [N], if the model takes one, is
+    repeated for every frame.  -> {"frames": f32 [N, steps, size, size], "commands": int64 [N, steps, G, S], "args": int64
+    [N, steps, G, S, 11]}: frame 0 is the icon of z1, the last frame that of z2.  Eval mode, no gradients; the model's
+    train / eval state is restored."""
+    if z1.shape != z2.shape or z1.dim() != 4 or not (z1.shape[1] == 1 and (z1.shape[0] == 1 or z1.shape[2] == 1)):
+        raise ValueError(f"interpolate: z1 and z2 both (N, 1, 1, dim_z) or both (1, 1, N, dim_z); got {tuple(z1.shape)} and "
+                         f"{tuple(z2.shape)}")
+    dim_z = z1.shape[-1]
+    za, zb = z1.detach().reshape(-1, 1, dim_z), z2.detach().reshape(-1, 1, dim_z)
+    N = za.shape[0]
+    a = interpolation_alphas(steps, ease, device=za.device).to(za.dtype).view(1, steps, 1)
+    z = ((1 - a) * za + a * zb).reshape(N * steps, 1, 1, dim_z)
+    if label is not None:
+        label = label.repeat_interleave(steps, dim=0)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            commands_y, args_y = model.greedy_sample(None, None, None, None, label=label, z=z, concat_groups=False,
+                                                     temperature=temperature)
+            frames = rasterize(commands_y, args_y, size=size, **raster)
+    finally:
+        model.train(was_training)
+    return {"frames": frames.view(N, steps, size, size), "commands": commands_y.reshape(N, steps, *commands_y.shape[1:]),
+            "args": args_y.reshape(N, steps, *args_y.shape[1:])}

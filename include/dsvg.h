@@ -47,8 +47,9 @@ extern "C" {
  * 13: dsvg_sample_points / dsvg_chamfer (+ dsvg_chamfer_workspace_bytes) added (reconstruction error of decoded icons, evaluation only); DSVG_I64.
  * 14: dsvg_chamfer_nn / dsvg_chamfer_bwd / dsvg_sample_points_bwd added (the gradient of the reconstruction error).
  * 15: dsvg_emd (+ dsvg_emd_workspace_bytes) / dsvg_emd_bwd / dsvg_polyline_length / dsvg_polyline_length_bwd added (the ordered
- *     point loss and the length losses of deepsvg/difflib/loss.py). */
-#define DSVG_ABI_VERSION 15
+ *     point loss and the length losses of deepsvg/difflib/loss.py).
+ * 16: dsvg_raster_segments (+ dsvg_raster_workspace_bytes) / dsvg_raster_sweep added (images of a decoded batch). */
+#define DSVG_ABI_VERSION 16
 
 const char* dsvg_last_error(void);
 int dsvg_version(void);
@@ -596,6 +597,55 @@ int dsvg_emd_bwd(const float* px, const int32_t* nx, int64_t capx, const int32_t
 int dsvg_polyline_length(const float* p, const int32_t* n, int64_t cap, int64_t B, float* out, void* stream);
 int dsvg_polyline_length_bwd(const float* p, const int32_t* n, int64_t cap, int64_t B, const float* dout, float* dp,
                              void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Images of a decoded batch (csrc/raster.hip): anti-aliased coverage images of the curves dsvg_sample_points samples, as
+ * outlines or filled.  Replaces SVG.draw -> cairosvg on the host, one icon at a time (deepsvg/svglib/svg.py:172-204; a
+ * filled path is drawn without a stroke, deepsvg/svglib/svg_primitive.py:34-38); the curves are those of
+ * SVGTensor.sample_points (deepsvg/difflib/tensor.py:191-230).  There is no rasteriser to match bit for bit; this is the
+ * definition (tests/raster_ref.py restates it in float64):
+ *  geometry: inputs as for dsvg_sample_points (itype, [B*G, L] commands, [B*G, L, 11] args, G * L <= 2048, 2 <= n <= 64):
+ *    `l` and `c` draw, nothing else does (`a` included, tensor.py:213); the start point of row i is the end position (args
+ *    9:11) of row i - 1 whatever it holds, (0, 0) on row 0.  A command becomes n - 1 chords between the vertices at z_k =
+ *    k / (n - 1): vertex 0 IS the start point and vertex n - 1 IS the row's end position, bit for bit (consecutive commands
+ *    share vertices exactly); between them `c` is the power-basis Horner form of dsvg_sample_points and `l` is
+ *    ((n - 1 - k) p0 + k p3) / (n - 1).
+ *  pixels: the image is size x size over the view box 0..256 (Bbox(256)); pitch s = 256 / size; the centre of pixel (row r,
+ *    column c) is ((c + 0.5) s, (r + 0.5) s): x is the column, y the row, y down as in SVG.
+ *  distance to a chord a -> b from p: t = clamp(((p - a) . (b - a)) / |b - a|^2, 0, 1) (t = 0 on a zero-length chord), q =
+ *    p - (a + t (b - a)), d^2 = q . q; the minimum is taken over d^2, one sqrt per pixel.
+ *  stroke (flags without DSVG_RASTER_FILL): d = the distance to the nearest chord of the image; ink = clamp(0.5 +
+ *    (stroke_width / 2 - d) / s, 0, 1).  An image without chords is all zeros.
+ *  fill (DSVG_RASTER_FILL): a sub-path is a maximal run of consecutive drawing rows of a sequence; each is closed by one
+ *    extra chord from its last vertex to its first.  A pixel is inside a sequence when its winding number with respect to
+ *    the sequence's chords is not 0 (non-zero, the SVG default), counted on a ray towards +x with the half-open rule: a
+ *    chord with ay <= cy < by counts +1, one with by <= cy < ay counts -1, each when its crossing lies at x > cx; inside
+ *    the image = inside any of its sequences.  d over all chords, closing chords included; ink = clamp(0.5 + d / s, 0, 1)
+ *    inside and clamp(0.5 - d / s, 0, 1) outside.
+ *  raster_segments: one workgroup per image writes its chord records in drawing order to `segs` (caller-owned,
+ *    dsvg_raster_workspace_bytes(B, G, L, n, fill) bytes, 4-byte aligned: cap = G * (L * (n - 1) + (fill ? (L + 1) / 2 : 0))
+ *    records per image) and their number to seg_counts int32 [B].  A record is 5 words: ax, ay, bx - ax, by - ay (fp32) and
+ *    a flags word: bit 0 = the first chord of a sequence; bits 1.. = on a closing chord, the number of records back to its
+ *    sub-path's first chord, 0 elsewhere.  Closing chords are written only with fill != 0, behind their sub-path.
+ *    What raster_sweep relies on in fill mode, for records from any producer: every record that is not a closing chord is
+ *    FOLLOWED by a record that starts at its end vertex (the next chord of its sub-path, or the closing chord), and a
+ *    closing chord ends at the start vertex of the record `back` records before it.  The sweep takes a chord's end y from
+ *    that record, not from ay + (by - ay), so that a vertex two chords share is ONE number and the half-open crossing rule
+ *    is watertight.  Where the rule is broken (a non-closing chord in the last record in use, or `back` larger than the
+ *    record's index) the sweep reads nothing out of bounds and falls back to ay + (by - ay) for that chord without a
+ *    diagnosis: the winding count is then watertight only up to rounding.
+ *  raster_sweep: segs / seg_counts as written above (cap records per image; counts are clamped into 0..cap) -> out fp32
+ *    [B, size, size], 1 = ink.  One workgroup per (image, tile of 32 x 32 pixels); 1 <= size <= 4096.  `flags` must
+ *    carry DSVG_RASTER_FILL exactly when the records were written with fill.  DSVG_RASTER_CULL: a wave skips the distance
+ *    work of a chord farther from its pixels than the distance at which ink saturates (stroke_width / 2 + s / 2, or s / 2 in
+ *    fill mode, plus a margin); the image is bit-identical with and without.  No atomics: bit-reproducible. */
+#define DSVG_RASTER_FILL 1
+#define DSVG_RASTER_CULL 2
+int64_t dsvg_raster_workspace_bytes(int64_t n_images, int32_t G, int32_t L, int32_t n, int32_t fill);
+int dsvg_raster_segments(int32_t itype, const void* commands, const void* args, int64_t B, int32_t G, int32_t L, int32_t n,
+                         int32_t fill, void* segs, int64_t segs_bytes, int32_t* seg_counts, void* stream);
+int dsvg_raster_sweep(const void* segs, const int32_t* seg_counts, int64_t B, int64_t cap, int32_t size, float stroke_width,
+                      int32_t flags, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The argument head fused with its consumers (csrc/head_fused.hip): args_fcn = Linear(256 -> n_args *
