@@ -12,6 +12,16 @@
 //                         (every lane reads the same address: a broadcast); running minimum of the SQUARED distance, one sqrt
 //                         per pixel after the sweep; in fill mode a running winding count per pixel, folded into an
 //                         `inside` bit at every sequence start.  No atomics, no scratch: bit-reproducible.
+//   dsvg_raster_sweep_nn  the same kernel with one more template flag: the running minimum also keeps the record index of the
+//                         chord that set it (a strict <: of equal d^2 the lowest index), stored where 0 < ink < 1, -1 elsewhere.
+// The gradient of an image (a pixel's ink depends on the chords only through the distance d to its nearest chord):
+//   dsvg_raster_sweep_bwd     a group of 16 or 64 lanes per chord walks the chord's bounding box, dilated by the reach the sweep
+//                             culls with and clipped to the image, in a fixed order; lanes accumulate the pixels whose saved
+//                             index is this chord (t and q recomputed with the sweep's expressions), a fixed-shape __shfl_xor
+//                             reduction, one lane stores d / d(ax, ay, bx, by).  A gather: no atomics, bit-reproducible.
+//   dsvg_raster_segments_bwd  the transpose of dsvg_raster_segments (linear in args): one workgroup per image, the forward's two
+//                             scans, one thread per token gathers its own command's chords, the next row's (whose start point
+//                             is this row's end position) and the closing chords that start or end at it, in float64.
 #include "dsvg_common.h"
 #include "flag_scan.h"
 #include "../../include/dsvg.h"
@@ -135,10 +145,13 @@ __global__ __launch_bounds__(SP_THREADS) void raster_segments_kernel(const T* __
 // shared vertex is one number.  With CULL a wave skips the distance work of a chord whose bounding box is farther from the
 // wave's 16 x 16 pixel centres than the distance at which ink saturates (plus a margin far above the rounding of either
 // side); such a chord cannot change a pixel.  The crossing test is never skipped.
-template <bool FILL, bool CULL>
+// NN: the minimum keeps the index of the record that set it (`idx` is not touched without NN); a chord culled for a wave is
+// farther from every pixel of the wave than the distance at which ink saturates, so the index of an unsaturated pixel is the
+// same with and without CULL.
+template <bool FILL, bool CULL, bool NN>
 __global__ __launch_bounds__(RS_THREADS) void raster_sweep_kernel(const float* __restrict__ segs, const int32_t* __restrict__ seg_counts,
                                                                   long long cap, int size, int tiles, float s, float half_w,
-                                                                  float* __restrict__ out) {
+                                                                  float* __restrict__ out, int32_t* __restrict__ idx) {
     __shared__ __attribute__((aligned(16))) float4 rec[RS_CHORDS * 2];
     __shared__ __attribute__((aligned(16))) float4 box[CULL ? RS_CHORDS : 1];
     const long long blk = blockIdx.x;
@@ -151,11 +164,12 @@ __global__ __launch_bounds__(RS_THREADS) void raster_sweep_kernel(const float* _
     const int col = col0 + (lane & 15), row = row0 + (lane >> 4);
     const float cx = ((float)col + 0.5f) * s;
     float cy[RS_PIX], m[RS_PIX];
-    int wind[RS_PIX], inside[RS_PIX];
+    int wind[RS_PIX], inside[RS_PIX], mi[RS_PIX];
 #pragma unroll
     for (int r = 0; r < RS_PIX; ++r) {
         cy[r] = ((float)(row + 4 * r) + 0.5f) * s;
         m[r] = INFINITY;
+        mi[r] = -1;
         wind[r] = 0;
         inside[r] = 0;
     }
@@ -211,7 +225,13 @@ __global__ __launch_bounds__(RS_THREADS) void raster_sweep_kernel(const float* _
                 if (near) {
                     const float t = fminf(fmaxf(fmaf(px, A.z, py * A.w) * B.x, 0.f), 1.f);
                     const float qx = fmaf(-t, A.z, px), qy = fmaf(-t, A.w, py);
-                    m[r] = fminf(m[r], fmaf(qx, qx, qy * qy));
+                    const float d2 = fmaf(qx, qx, qy * qy);
+                    if (NN) {             // the value fminf keeps (d2 >= +0; a NaN loses either way), and who set it
+                        if (d2 < m[r]) {
+                            m[r] = d2;
+                            mi[r] = j0 + jl;
+                        }
+                    } else m[r] = fminf(m[r], d2);
                 }
             }
         };
@@ -248,7 +268,165 @@ __global__ __launch_bounds__(RS_THREADS) void raster_sweep_kernel(const float* _
         float ink;
         if (FILL) ink = (inside[r] | (wind[r] != 0)) ? 0.5f + d / s : 0.5f - d / s;
         else ink = 0.5f + (half_w - d) / s;
-        out[(b * size + (row + 4 * r)) * size + col] = fminf(fmaxf(ink, 0.f), 1.f);
+        ink = fminf(fmaxf(ink, 0.f), 1.f);
+        out[(b * size + (row + 4 * r)) * size + col] = ink;
+        if (NN) idx[(b * size + (row + 4 * r)) * size + col] = ink > 0.f && ink < 1.f ? mi[r] : -1;
+    }
+}
+
+constexpr int RB_THREADS = 256;
+
+// One group of GW lanes (16, or a whole wave) per chord record j of image b.  The chord can be the saved nearest chord only
+// of pixels whose ink is not saturated, i.e. whose centre lies within `reach` (the sweep's culling distance) of the chord's
+// bounding box: the group walks that box, clipped to the image and one pixel wider against rounding, row-major with stride
+// GW.  For a pixel with idx == j and 0 < ink < 1 as stored: t, q, d^2 by the sweep's expressions, d ink / d d = -1 / s (stroke
+// and fill outside, ink <= 0.5) or +1 / s (fill inside), d d / d a = -(1 - t) q / d, d d / d b = -t q / d; d == 0 contributes
+// nothing.  Every record below the image's count is written (zeros where no pixel points at it).
+template <bool FILL, int GW>
+__global__ __launch_bounds__(RB_THREADS) void raster_sweep_bwd_kernel(const float* __restrict__ segs, const int32_t* __restrict__ seg_counts,
+                                                                      const float* __restrict__ out, const int32_t* __restrict__ idx,
+                                                                      const float* __restrict__ dout, long long cap, int size,
+                                                                      int blocks_per_image, float s, float reach,
+                                                                      float* __restrict__ dsegs) {
+    constexpr int PER = RB_THREADS / GW;                  // chords of a workgroup
+    const long long b = blockIdx.x / blocks_per_image;
+    const int j = (int)(blockIdx.x % blocks_per_image) * PER + (int)threadIdx.x / GW;
+    const int l = (int)threadIdx.x % GW;
+    const int cnt = (int)min((long long)max(seg_counts[b], 0), cap);
+    if (j >= cnt) return;                                 // whole groups leave: the shuffles below stay inside a group
+    const float* r = segs + (b * cap + j) * RS_REC;
+    const float ax = r[0], ay = r[1], dx = r[2], dy = r[3];
+    const float len2 = fmaf(dx, dx, dy * dy);
+    const float inv = len2 > 1e-30f ? 1.f / len2 : 0.f;
+    // pixel k has its centre at (k + 0.5) s; a NaN or an infinite vertex clamps to an empty or a full range, in bounds
+    const float fsize = (float)size;
+    auto first = [&](float v) { return (int)fminf(fmaxf(floorf((v - reach) / s - 0.5f), 0.f), fsize); };
+    auto end = [&](float v) { return (int)fminf(fmaxf(ceilf((v + reach) / s - 0.5f) + 1.f, 0.f), fsize); };
+    const int c0 = first(fminf(ax, ax + dx)), c1 = end(fmaxf(ax, ax + dx));
+    const int r0 = first(fminf(ay, ay + dy)), r1 = end(fmaxf(ay, ay + dy));
+    const int w = c1 - c0, np = w > 0 && r1 > r0 ? w * (r1 - r0) : 0;          // <= 4096^2
+    const float* ob = out + b * size * size;
+    const int32_t* ib = idx + b * size * size;
+    const float* gb = dout + b * size * size;
+    float sax = 0.f, say = 0.f, sbx = 0.f, sby = 0.f;
+    for (int p = l; p < np; p += GW) {
+        const int pr = p / w;
+        const int row = r0 + pr, col = c0 + (p - pr * w);
+        const long long pix = (long long)row * size + col;
+        if (ib[pix] != j) continue;
+        const float ink = ob[pix];
+        if (!(ink > 0.f && ink < 1.f)) continue;
+        const float px = ((float)col + 0.5f) * s - ax, py = ((float)row + 0.5f) * s - ay;
+        const float t = fminf(fmaxf(fmaf(px, dx, py * dy) * inv, 0.f), 1.f);
+        const float qx = fmaf(-t, dx, px), qy = fmaf(-t, dy, py);
+        const float d2 = fmaf(qx, qx, qy * qy);
+        if (!(d2 > 0.f)) continue;
+        const float g = (FILL && ink > 0.5f ? gb[pix] : -gb[pix]) / (s * sqrtf(d2));          // dL/dd / d
+        const float gx = g * qx, gy = g * qy;
+        sax = fmaf(t - 1.f, gx, sax); say = fmaf(t - 1.f, gy, say);
+        sbx = fmaf(-t, gx, sbx); sby = fmaf(-t, gy, sby);
+    }
+#pragma unroll
+    for (int o = GW / 2; o; o >>= 1) {
+        sax += __shfl_xor(sax, o, GW); say += __shfl_xor(say, o, GW);
+        sbx += __shfl_xor(sbx, o, GW); sby += __shfl_xor(sby, o, GW);
+    }
+    if (l == 0) reinterpret_cast<float4*>(dsegs)[b * cap + j] = make_float4(sax, say, sbx, sby);
+}
+
+// The transpose of raster_segments_kernel<float>: dargs[b, t, :] from the vertex gradients dsegs[b, :, :] = d / d(ax, ay, bx,
+// by) of every record.  The offsets are the forward's.  Vertex q of a command is the a of its chord q and the b of its chord
+// q - 1; its weights are the Bernstein ones for `c` (what the forward's Horner form evaluates) and ((n - 1 - q), q) / (n - 1)
+// for `l`, with vertex 0 the start point and vertex n - 1 the end position themselves.  A token sums, in this order: its own
+// command's vertices (control1, control2, end), the vertices of the command on the row after it (whose start point is this
+// row's end position, whatever this row holds; row 0's start is the constant (0, 0)), the a of the closing chord of the
+// sub-path that ends at it and the b of the closing chord of the sub-path that starts on the row after it.  float64 sums,
+// as sample_points_bwd_kernel; records at or past seg_counts[b] read as zero.  Every element of the row is written.
+__global__ __launch_bounds__(SP_THREADS) void raster_segments_bwd_kernel(const float* __restrict__ commands, const float* __restrict__ dsegs,
+                                                                         const int32_t* __restrict__ seg_counts, int G, int L, int n,
+                                                                         int fill, long long cap, float* __restrict__ dargs) {
+    __shared__ int pre[SP_MAX_TOK + 1];
+    __shared__ int cl[SP_MAX_TOK + 1];
+    __shared__ int last[SP_MAX_TOK];          // last token of the q-th sub-path
+    __shared__ int wtot[SP_MAX_TOK / 64];
+    const long long b = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int T_ = G * L;
+    const float* cmd = commands + b * T_;
+    block_flag_scan(T_, pre, wtot, [&](int t) {
+        if (t >= T_) return false;
+        const int c = (int)cmd[t];
+        return c == RS_CMD_L || c == RS_CMD_C;
+    });
+    block_flag_scan(T_, cl, wtot, [&](int t) {
+        if (!fill || t >= T_ || pre[t + 1] == pre[t]) return false;
+        return t % L == L - 1 || pre[t + 2] == pre[t + 1];
+    });
+    for (int t = tid; t < T_; t += SP_THREADS)
+        if (cl[t + 1] > cl[t]) last[cl[t]] = t;
+    __syncthreads();
+    const int cnt = (int)min((long long)max(seg_counts[b], 0), cap);
+    const float4* ds = reinterpret_cast<const float4*>(dsegs) + b * cap;
+    auto rec = [&](int o) { return o < cnt ? ds[o] : make_float4(0.f, 0.f, 0.f, 0.f); };
+    float* out = dargs + b * T_ * RS_N_ARGS;
+    const double step = 1.0 / (double)(n - 1);
+    for (int t = tid; t < T_; t += SP_THREADS) {
+        const int i = t % L;
+        double c1x = 0.0, c1y = 0.0, c2x = 0.0, c2y = 0.0, ex = 0.0, ey = 0.0;
+        const bool draws = pre[t + 1] > pre[t];
+        if (draws) {
+            const bool cubic = (int)cmd[t] == RS_CMD_C;
+            const int o = pre[t] * (n - 1) + cl[t];
+            for (int q = 1; q < n; ++q) {                  // (vertex 0 has no weight on this row)
+                const float4 lo = rec(o + q - 1);
+                double vx = (double)lo.z, vy = (double)lo.w;
+                if (q < n - 1) {
+                    const float4 hi = rec(o + q);
+                    vx += (double)hi.x; vy += (double)hi.y;
+                }
+                const double z = q == n - 1 ? 1.0 : (double)q * step, w = 1.0 - z;
+                if (cubic) {
+                    const double w1 = 3.0 * w * w * z, w2 = 3.0 * w * z * z, w3 = z * z * z;
+                    c1x += w1 * vx; c1y += w1 * vy;
+                    c2x += w2 * vx; c2y += w2 * vy;
+                    ex += w3 * vx; ey += w3 * vy;
+                } else {
+                    ex += z * vx; ey += z * vy;
+                }
+            }
+        }
+        const bool next_draws = i + 1 < L && pre[t + 2] > pre[t + 1];
+        if (next_draws) {
+            const bool cubic = (int)cmd[t + 1] == RS_CMD_C;
+            const int o = pre[t + 1] * (n - 1) + cl[t + 1];
+            for (int q = 0; q < n - 1; ++q) {              // (vertex n - 1 has no weight on the start point)
+                const float4 hi = rec(o + q);
+                double vx = (double)hi.x, vy = (double)hi.y;
+                if (q > 0) {
+                    const float4 lo = rec(o + q - 1);
+                    vx += (double)lo.z; vy += (double)lo.w;
+                }
+                const double w = 1.0 - (double)q * step;
+                const double w0 = cubic ? w * w * w : w;
+                ex += w0 * vx; ey += w0 * vy;
+            }
+        }
+        if (fill) {
+            if (cl[t + 1] > cl[t]) {                       // a sub-path ends here: its closing chord starts at this end position
+                const float4 c = rec((pre[t] + 1) * (n - 1) + cl[t]);
+                ex += (double)c.x; ey += (double)c.y;
+            }
+            if (next_draws && !draws) {                    // a sub-path starts on the next row: its closing chord ends here
+                const int te = last[cl[t + 1]];
+                const float4 c = rec((pre[te] + 1) * (n - 1) + cl[te]);
+                ex += (double)c.z; ey += (double)c.w;
+            }
+        }
+        float* row = out + (long long)t * RS_N_ARGS;
+#pragma unroll
+        for (int q = 0; q < 5; ++q) row[q] = 0.f;
+        row[5] = (float)c1x; row[6] = (float)c1y; row[7] = (float)c2x; row[8] = (float)c2y;
+        row[9] = (float)ex; row[10] = (float)ey;
     }
 }
 }  // namespace
@@ -281,30 +459,97 @@ extern "C" int dsvg_raster_segments(int32_t itype, const void* commands, const v
     return 0;
 }
 
-extern "C" int dsvg_raster_sweep(const void* segs, const int32_t* seg_counts, int64_t B, int64_t cap, int32_t size,
-                                 float stroke_width, int32_t flags, float* out, void* stream) {
-    DSVG_CHECK_ARG(size >= 1 && size <= RS_MAX_SIZE, "raster_sweep: size = %d pixels per side, need 1..%d", size, RS_MAX_SIZE);
-    DSVG_CHECK_ARG(segs && seg_counts && out, "raster_sweep: null pointer");
-    DSVG_CHECK_ARG(stroke_width >= 0.f && stroke_width < 1e6f, "raster_sweep: stroke_width %g, need a finite width >= 0",
+namespace {
+// the arguments dsvg_raster_sweep, _nn and _bwd share, refused under the name of the caller
+int sweep_args_ok(const char* name, bool pointers, int64_t B, int64_t cap, int32_t size, float stroke_width, int32_t flags,
+                  int32_t known_flags, int64_t groups) {
+    DSVG_CHECK_ARG(size >= 1 && size <= RS_MAX_SIZE, "%s: size = %d pixels per side, need 1..%d", name, size, RS_MAX_SIZE);
+    DSVG_CHECK_ARG(pointers, "%s: null pointer", name);
+    DSVG_CHECK_ARG(stroke_width >= 0.f && stroke_width < 1e6f, "%s: stroke_width %g, need a finite width >= 0", name,
                    (double)stroke_width);
-    DSVG_CHECK_ARG((flags & ~(DSVG_RASTER_FILL | DSVG_RASTER_CULL)) == 0, "raster_sweep: unknown flags 0x%x", flags);
+    DSVG_CHECK_ARG((flags & ~known_flags) == 0, "%s: unknown flags 0x%x", name, flags);
+    DSVG_CHECK_ARG(B > 0 && cap > 0 && cap < (1ll << 26) && B * groups < (1ll << 31),
+                   "%s: bad shape (B=%lld cap=%lld: %lld workgroups; chords per image below 2^26, workgroups below 2^31)", name,
+                   (long long)B, (long long)cap, (long long)(B * groups));
+    return 0;
+}
+
+int sweep_launch(const char* name, const void* segs, const int32_t* seg_counts, int64_t B, int64_t cap, int32_t size,
+                 float stroke_width, int32_t flags, float* out, int32_t* idx, bool nn, void* stream) {
     const int64_t tiles = (size + RS_TILE - 1) / RS_TILE;
-    DSVG_CHECK_ARG(B > 0 && cap > 0 && cap < (1ll << 26) && B * tiles * tiles < (1ll << 31),
-                   "raster_sweep: bad shape (B=%lld cap=%lld: %lld workgroups; chords per image below 2^26, workgroups below "
-                   "2^31)", (long long)B, (long long)cap, (long long)(B * tiles * tiles));
+    if (sweep_args_ok(name, segs && seg_counts && out && (idx || !nn), B, cap, size, stroke_width, flags,
+                      DSVG_RASTER_FILL | DSVG_RASTER_CULL, tiles * tiles))
+        return -1;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)(B * tiles * tiles)), block(RS_THREADS);
     const float s = 256.f / (float)size, half_w = 0.5f * stroke_width;
     const float* sg = (const float*)segs;
     const bool fill = flags & DSVG_RASTER_FILL, cull = flags & DSVG_RASTER_CULL;
-#define RS_LAUNCH(F, C)                                                                                                  \
-    hipLaunchKernelGGL((raster_sweep_kernel<F, C>), grid, block, 0, st, sg, seg_counts, (long long)cap, size, (int)tiles, s, \
-                       half_w, out)
-    if (fill && cull) RS_LAUNCH(true, true);
-    else if (fill) RS_LAUNCH(true, false);
-    else if (cull) RS_LAUNCH(false, true);
-    else RS_LAUNCH(false, false);
+#define RS_LAUNCH(F, C, N)                                                                                                  \
+    hipLaunchKernelGGL((raster_sweep_kernel<F, C, N>), grid, block, 0, st, sg, seg_counts, (long long)cap, size, (int)tiles, s, \
+                       half_w, out, idx)
+#define RS_LAUNCH_NN(F, C)  \
+    do {                    \
+        if (nn) RS_LAUNCH(F, C, true); \
+        else RS_LAUNCH(F, C, false);   \
+    } while (0)
+    if (fill && cull) RS_LAUNCH_NN(true, true);
+    else if (fill) RS_LAUNCH_NN(true, false);
+    else if (cull) RS_LAUNCH_NN(false, true);
+    else RS_LAUNCH_NN(false, false);
+#undef RS_LAUNCH_NN
 #undef RS_LAUNCH
-    DSVG_LAUNCH_CHECK("raster_sweep");
+    DSVG_LAUNCH_CHECK(name);
+    return 0;
+}
+}  // namespace
+
+extern "C" int dsvg_raster_sweep(const void* segs, const int32_t* seg_counts, int64_t B, int64_t cap, int32_t size,
+                                 float stroke_width, int32_t flags, float* out, void* stream) {
+    return sweep_launch("raster_sweep", segs, seg_counts, B, cap, size, stroke_width, flags, out, nullptr, false, stream);
+}
+
+extern "C" int dsvg_raster_sweep_nn(const void* segs, const int32_t* seg_counts, int64_t B, int64_t cap, int32_t size,
+                                    float stroke_width, int32_t flags, float* out, int32_t* idx, void* stream) {
+    return sweep_launch("raster_sweep_nn", segs, seg_counts, B, cap, size, stroke_width, flags, out, idx, true, stream);
+}
+
+extern "C" int dsvg_raster_sweep_bwd(const void* segs, const int32_t* seg_counts, const float* out, const int32_t* idx,
+                                     const float* dout, int64_t B, int64_t cap, int32_t size, float stroke_width, int32_t flags,
+                                     float* dsegs, void* stream) {
+    const bool fill = flags & DSVG_RASTER_FILL, wide = flags & DSVG_RASTER_WIDE;
+    const int per = RB_THREADS / (wide ? 64 : 16);
+    const int64_t bpi = (cap + per - 1) / per;
+    if (sweep_args_ok("raster_sweep_bwd", segs && seg_counts && out && idx && dout && dsegs, B, cap, size, stroke_width, flags,
+                      DSVG_RASTER_FILL | DSVG_RASTER_WIDE, bpi))
+        return -1;
+    DSVG_CHECK_ARG(((uintptr_t)dsegs & 15) == 0, "raster_sweep_bwd: dsegs must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)(B * bpi)), block(RB_THREADS);
+    const float s = 256.f / (float)size;
+    const float reach = (fill ? 0.5f * s : 0.5f * stroke_width + 0.5f * s) * 1.001f + 0.01f;      // as raster_sweep_kernel culls
+#define RB_LAUNCH(F, W)                                                                                                  \
+    hipLaunchKernelGGL((raster_sweep_bwd_kernel<F, W>), grid, block, 0, st, (const float*)segs, seg_counts, out, idx, dout, \
+                       (long long)cap, size, (int)bpi, s, reach, dsegs)
+    if (fill && wide) RB_LAUNCH(true, 64);
+    else if (fill) RB_LAUNCH(true, 16);
+    else if (wide) RB_LAUNCH(false, 64);
+    else RB_LAUNCH(false, 16);
+#undef RB_LAUNCH
+    DSVG_LAUNCH_CHECK("raster_sweep_bwd");
+    return 0;
+}
+
+extern "C" int dsvg_raster_segments_bwd(const float* commands, const float* dsegs, const int32_t* seg_counts, int64_t B,
+                                        int32_t G, int32_t L, int32_t n, int32_t fill, float* dargs, void* stream) {
+    DSVG_CHECK_ARG(commands && dsegs && seg_counts && dargs, "raster_segments_bwd: null pointer");
+    DSVG_CHECK_ARG(n >= 2 && n <= 64, "raster_segments_bwd: n = %d points per command, need 2..64", n);
+    DSVG_CHECK_ARG(B > 0 && B < (1ll << 31) && G >= 1 && L >= 1 && (int64_t)G * L <= SP_MAX_TOK,
+                   "raster_segments_bwd: bad shape (B=%lld G=%d L=%d; G * L <= %d tokens per image)", (long long)B, G, L,
+                   SP_MAX_TOK);
+    DSVG_CHECK_ARG(((uintptr_t)dsegs & 15) == 0, "raster_segments_bwd: dsegs must be 16-byte aligned");
+    hipLaunchKernelGGL(raster_segments_bwd_kernel, dim3((unsigned)B), dim3(SP_THREADS), 0, (hipStream_t)stream, commands, dsegs,
+                       seg_counts, G, L, n, fill ? 1 : 0, (long long)raster_cap(G, L, n, fill), dargs);
+    DSVG_LAUNCH_CHECK("raster_segments_bwd");
     return 0;
 }

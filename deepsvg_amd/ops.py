@@ -1404,6 +1404,68 @@ def rasterize(commands, args, size=64, stroke_width=3.2, fill=False, n=10, group
     return raster_sweep(segs, seg_counts, size=size, stroke_width=stroke_width, fill=fill, cull=cull)
 
 
+RASTER_BWD_WIDE = False      # the default of raster_sweep_bwd's `wide`: 16 lanes per chord are faster on three of the four
+                             # configurations of profiles/raster_grad_bench.log (a wave per chord wins at fill, 128 pixels)
+
+
+def _chk_records(segs, seg_counts):
+    _chk(segs, seg_counts)
+    assert segs.dtype == torch.float32 and segs.dim() == 3 and segs.shape[2] == 5 and segs.is_contiguous()
+    assert seg_counts.dtype == torch.int32 and seg_counts.shape == (segs.shape[0],) and seg_counts.is_contiguous()
+    return segs.shape[0], segs.shape[1]
+
+
+def raster_sweep_nn(segs, seg_counts, size=64, stroke_width=3.2, fill=False, cull=None):
+    """raster_sweep that also returns the arg-min -> (out f32 [B, size, size] with raster_sweep's bits, idx int32 [B, size,
+    size]: the record index of the pixel's nearest chord where 0 < out < 1 (ties go to the lowest index), -1 everywhere
+    else); idx is the same with and without `cull`"""
+    B, cap = _chk_records(segs, seg_counts)
+    flags = (_l.DSVG_RASTER_FILL if fill else 0) | (_l.DSVG_RASTER_CULL if (RASTER_CULL if cull is None else cull) else 0)
+    out = torch.empty(B, int(size), int(size), dtype=torch.float32, device=segs.device)
+    idx = torch.empty(B, int(size), int(size), dtype=torch.int32, device=segs.device)
+    _l.check(_l.load().dsvg_raster_sweep_nn(segs.data_ptr(), seg_counts.data_ptr(), B, cap, int(size), float(stroke_width),
+                                            flags, out.data_ptr(), idx.data_ptr(), _stream()), "dsvg_raster_sweep_nn")
+    return out, idx
+
+
+def raster_sweep_bwd(segs, seg_counts, out, idx, dout, stroke_width=3.2, fill=False, wide=None):
+    """the records, image and indices of raster_sweep_nn (same stroke_width and fill), dout f32 [B, size, size] -> dsegs f32
+    [B, cap, 4]: the gradient with respect to the vertices (ax, ay, bx, by) of every record; rows below seg_counts[b] are all
+    written, rows past it are not.  `wide` (None: RASTER_BWD_WIDE): a wave per chord instead of 16 lanes"""
+    B, cap = _chk_records(segs, seg_counts)
+    _chk(out, idx, dout)
+    size = out.shape[-1]
+    assert out.dtype == torch.float32 and out.shape == (B, size, size) and out.is_contiguous()
+    assert idx.dtype == torch.int32 and idx.shape == out.shape and idx.is_contiguous()
+    assert dout.dtype == torch.float32 and dout.shape == out.shape and dout.is_contiguous()
+    flags = (_l.DSVG_RASTER_FILL if fill else 0) | (_l.DSVG_RASTER_WIDE if (RASTER_BWD_WIDE if wide is None else wide) else 0)
+    dsegs = torch.empty(B, cap, 4, dtype=torch.float32, device=segs.device)
+    _l.check(_l.load().dsvg_raster_sweep_bwd(segs.data_ptr(), seg_counts.data_ptr(), out.data_ptr(), idx.data_ptr(),
+                                             dout.data_ptr(), B, cap, size, float(stroke_width), flags, dsegs.data_ptr(),
+                                             _stream()), "dsvg_raster_sweep_bwd")
+    return dsegs
+
+
+def raster_segments_bwd(commands, dsegs, seg_counts, n=10, groups=1, fill=False):
+    """float32 commands [B*groups, L], dsegs f32 [B, cap, 4] as raster_sweep_bwd returns it and the seg_counts of
+    raster_segments (same n, groups, fill) -> dargs f32 [B*groups, L, 11], every element written (integer inputs have no
+    gradient)"""
+    _chk(commands, dsegs, seg_counts)
+    assert commands.dim() == 2 and commands.dtype == torch.float32 and commands.is_contiguous(), \
+        "raster_segments_bwd: float32 commands [B*groups, L]"
+    assert groups >= 1 and commands.shape[0] % groups == 0 and commands.shape[0] >= groups
+    B, L = commands.shape[0] // groups, commands.shape[1]
+    lib = _l.load()
+    cap = lib.dsvg_raster_workspace_bytes(B, groups, L, int(n), int(bool(fill))) // (20 * B)      # (0 for an n the call refuses)
+    assert dsegs.dtype == torch.float32 and dsegs.shape == (B, max(cap, 1), 4) and dsegs.is_contiguous(), \
+        f"raster_segments_bwd: dsegs {tuple(dsegs.shape)}"
+    assert seg_counts.dtype == torch.int32 and seg_counts.shape == (B,) and seg_counts.is_contiguous()
+    dargs = torch.empty(commands.shape[0], L, 11, dtype=torch.float32, device=commands.device)
+    _l.check(lib.dsvg_raster_segments_bwd(commands.data_ptr(), dsegs.data_ptr(), seg_counts.data_ptr(), B, groups, L, int(n),
+                                          int(bool(fill)), dargs.data_ptr(), _stream()), "dsvg_raster_segments_bwd")
+    return dargs
+
+
 # ------------------------------------------------------------------------------------------------
 # device-side batch assembly (svgtensor_dataset.py:164-205)
 # ------------------------------------------------------------------------------------------------

@@ -9,15 +9,29 @@ become n - 1 chords each; the view box is 0..256 argument units (``Bbox(256)``),
 ((c + 0.5) s, (r + 0.5) s) with s = 256 / size, y down.  Stroke mode (the reference's default): ink = clamp(0.5 +
 (stroke_width / 2 - d) / s, 0, 1) with d the distance to the nearest chord.  Fill mode (no stroke, as
 svglib/svg_primitive.py:34-38): every sub-path is closed, a pixel is inside an image when its non-zero winding number with
-respect to any ONE sequence's chords is not 0, and ink = clamp(0.5 +- d / s, 0, 1).  No atomics: bit-reproducible.  No
-gradient: a differentiable rasteriser is a separate piece of work.  The reference's per-path `filling` values, colours and
-the visualisation extras of ``draw`` are not drawn; arcs are not either (the reference's own sampler skips them).
+respect to any ONE sequence's chords is not 0, and ink = clamp(0.5 +- d / s, 0, 1).  No atomics: bit-reproducible.
+`rasterize` carries no gradient; `rasterize_with_grad` draws the same bits and does (below).  The reference's per-path
+`filling` values, colours and the visualisation extras of ``draw`` are not drawn; arcs are not either (the reference's own
+sampler skips them).
+
+The gradient of an image with respect to float32 `args` (`rasterize_with_grad`, `image_loss`, `refine_to_images`; three
+more kernels of csrc/raster.hip, tests/raster_grad_ref.py restates them in float64): a pixel's ink depends on the chords only
+through d, the distance to its nearest chord a -> b with the closest point at the clamped parameter t and q = p - (a + t
+(b - a)): d d / d a = -(1 - t) q / d, d d / d b = -t q / d; d ink / d d = -1 / s (stroke, and fill outside), +1 / s (fill inside,
+ink > 0.5), 0 where ink is clamped; the winding number is piecewise constant and carries none.  Of chords at equal fp32
+d^2 the one with the lowest index takes the term; a pixel with d == 0 contributes nothing (in fill mode the limit exists but
+needs an orientation the sweep does not carry: a shape whose unsaturated pixels all sit ON the outline, like the integer
+square of INTEGRATION.md section 6 at size 64, has an exactly zero gradient); saturation is read from the stored image.
+Chord vertices are linear in `args`; the start point of a command is the end position of the row before it whatever that
+row holds, and columns 0-4, padding and rows that neither draw nor precede a drawing row get exact zeros.  A gather with
+an arg-min saved by the forward: no atomics, bit-reproducible.
 """
 import torch
 
 from . import ops
 
-__all__ = ["rasterize", "reconstruction_images", "interpolate", "interpolation_alphas"]
+__all__ = ["rasterize", "rasterize_with_grad", "image_loss", "refine_to_images", "reconstruction_images", "interpolate",
+           "interpolation_alphas"]
 
 
 def rasterize(commands, args, size=64, stroke_width=3.2, fill=False, n=10):
@@ -43,6 +57,81 @@ def rasterize(commands, args, size=64, stroke_width=3.2, fill=False, n=10):
     S = commands.shape[-1]
     commands, args = commands.reshape(-1, S).contiguous(), args.reshape(-1, S, args.shape[-1]).contiguous()
     return ops.rasterize(commands, args, size=size, stroke_width=stroke_width, fill=fill, n=n, groups=groups)
+
+
+class _Rasterize(torch.autograd.Function):
+    """raster_segments -> raster_sweep_nn; backward raster_sweep_bwd -> raster_segments_bwd"""
+
+    @staticmethod
+    def forward(ctx, commands, args, size, stroke_width, fill, n, groups):
+        segs, seg_counts = ops.raster_segments(commands, args, n=n, groups=groups, fill=fill)
+        out, idx = ops.raster_sweep_nn(segs, seg_counts, size=size, stroke_width=stroke_width, fill=fill)
+        ctx.save_for_backward(commands, segs, seg_counts, out, idx)
+        ctx.raster = (stroke_width, fill, n, groups)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        commands, segs, seg_counts, out, idx = ctx.saved_tensors
+        stroke_width, fill, n, groups = ctx.raster
+        dsegs = ops.raster_sweep_bwd(segs, seg_counts, out, idx, dout.contiguous(), stroke_width=stroke_width, fill=fill)
+        dargs = ops.raster_segments_bwd(commands, dsegs, seg_counts, n=n, groups=groups, fill=fill)
+        return None, dargs, None, None, None, None, None
+
+
+def rasterize_with_grad(commands, args, size=64, stroke_width=3.2, fill=False, n=10):
+    """`rasterize` for float32 `args` that receive a gradient: the same shapes, the same image bit for bit, and
+    d image / d args flows back (module docstring: formulas and conventions).  `commands` of any dtype are read as float32;
+    the backward is not differentiable again."""
+    if commands.dim() not in (2, 3) or args.dim() != commands.dim() + 1 or args.shape[:-1] != commands.shape:
+        raise ValueError(f"rasterize_with_grad: commands (N, S) or (N, G, S) with args (..., S, 11); got "
+                         f"{tuple(commands.shape)} and {tuple(args.shape)}")
+    if args.dtype != torch.float32:
+        raise ValueError(f"rasterize_with_grad: float32 args (integer arguments have no gradient); got {args.dtype}")
+    groups = commands.shape[1] if commands.dim() == 3 else 1
+    S = commands.shape[-1]
+    commands, args = commands.detach().float().reshape(-1, S).contiguous(), args.reshape(-1, S, args.shape[-1]).contiguous()
+    return _Rasterize.apply(commands, args, int(size), float(stroke_width), bool(fill), int(n), groups)
+
+
+def image_loss(commands, args, target_images, **raster):
+    """Mean squared ink difference between the images of `commands` / `args` and `target_images` f32 [N, size, size] (the size
+    is the target's) -> {"loss": 0-d, the batch mean; "per_icon": [N]}.  Differentiable with respect to float32 `args`.
+    `raster`: stroke_width, fill, n of `rasterize`."""
+    if target_images.dim() != 3 or target_images.shape[-1] != target_images.shape[-2]:
+        raise ValueError(f"image_loss: target_images (N, size, size); got {tuple(target_images.shape)}")
+    images = rasterize_with_grad(commands, args, size=target_images.shape[-1], **raster)
+    if images.shape != target_images.shape:
+        raise ValueError(f"image_loss: {images.shape[0]} images against {target_images.shape[0]} targets")
+    per_icon = (images - target_images.detach().to(images.dtype)).pow(2).flatten(1).mean(1)
+    return {"loss": per_icon.mean(), "per_icon": per_icon}
+
+
+def refine_to_images(commands, args, target_images, steps=150, lr=0.1, **raster):
+    """The Adam loop of `metrics.refine` against pictures instead of point clouds: minimises `image_loss` on a float32 copy of
+    `args` -> (refined args f32, history f32 [steps]: the loss before each step, kept on the device - the loop reads nothing
+    back).  `target_images`: one tensor [N, size, size], or a list of such tensors of different sizes whose losses are summed.
+    The gradient is local: only pixels within about one pixel of the outline (where ink is not saturated) pull on it, so the
+    outline has to start within a pixel or so of where the target has ink to be drawn to it.  A coarse target widens that
+    basin (a pixel of a 16 x 16 image is 16 argument units); a list from coarse to fine gives both reach and precision.
+    Elements whose gradient is always zero (columns 0-4, padding, rows that neither draw nor precede a drawing row) come
+    back as they went in."""
+    targets = [target_images] if torch.is_tensor(target_images) else list(target_images)
+    if not targets:
+        raise ValueError("refine_to_images: no target images")
+    refined = args.detach().float().clone().requires_grad_(True)
+    opt = torch.optim.Adam([refined], lr=lr)
+    history = torch.empty(steps, dtype=torch.float32, device=refined.device)
+    for step in range(steps):
+        opt.zero_grad(set_to_none=True)
+        value = image_loss(commands, refined, targets[0], **raster)["loss"]
+        for target in targets[1:]:
+            value = value + image_loss(commands, refined, target, **raster)["loss"]
+        value.backward()
+        history[step] = value.detach()
+        opt.step()
+    return refined.detach(), history
 
 
 def reconstruction_images(model, commands, args, label=None, size=64, temperature=0.0, **raster):

@@ -48,8 +48,9 @@ extern "C" {
  * 14: dsvg_chamfer_nn / dsvg_chamfer_bwd / dsvg_sample_points_bwd added (the gradient of the reconstruction error).
  * 15: dsvg_emd (+ dsvg_emd_workspace_bytes) / dsvg_emd_bwd / dsvg_polyline_length / dsvg_polyline_length_bwd added (the ordered
  *     point loss and the length losses of deepsvg/difflib/loss.py).
- * 16: dsvg_raster_segments (+ dsvg_raster_workspace_bytes) / dsvg_raster_sweep added (images of a decoded batch). */
-#define DSVG_ABI_VERSION 16
+ * 16: dsvg_raster_segments (+ dsvg_raster_workspace_bytes) / dsvg_raster_sweep added (images of a decoded batch).
+ * 17: dsvg_raster_sweep_nn / dsvg_raster_sweep_bwd / dsvg_raster_segments_bwd added (the gradient of an image). */
+#define DSVG_ABI_VERSION 17
 
 const char* dsvg_last_error(void);
 int dsvg_version(void);
@@ -646,6 +647,35 @@ int dsvg_raster_segments(int32_t itype, const void* commands, const void* args, 
                          int32_t fill, void* segs, int64_t segs_bytes, int32_t* seg_counts, void* stream);
 int dsvg_raster_sweep(const void* segs, const int32_t* seg_counts, int64_t B, int64_t cap, int32_t size, float stroke_width,
                       int32_t flags, float* out, void* stream);
+/* The gradient of an image with respect to the arguments (ABI 17).  A pixel's ink depends on the chords only through d, the
+ * distance to its nearest chord j* (a -> b, closest point at the clamped parameter t, q = p - (a + t (b - a)), d = |q|):
+ * d d / d a = -(1 - t) q / d and d d / d b = -t q / d (interior t: q is normal to b - a; clamped t: t is constant); d ink / d d
+ * = -1 / s in stroke mode and in fill mode outside, +1 / s in fill mode inside (ink > 0.5), 0 where ink is clamped.  The
+ * winding number is piecewise constant and carries no gradient.  Conventions: of chords at equal fp32 d^2 the lowest record
+ * index takes the term; a pixel with d == 0 contributes nothing (the peak of the ink in stroke mode; in fill mode the limit
+ * needs an orientation the sweep does not carry); saturation (ink == 0 or ink == 1) is read from the stored image.
+ *  raster_sweep_nn: dsvg_raster_sweep that also writes idx int32 [B, size, size]: the record index of the pixel's nearest
+ *    chord where 0 < out < 1, -1 everywhere else (every pixel of an image without chords included).  `out` has the bits of
+ *    dsvg_raster_sweep, and idx is the same with and without DSVG_RASTER_CULL (a chord culled for a wave is out of reach of
+ *    every unsaturated pixel of that wave).
+ *  raster_sweep_bwd: the records, out and idx of raster_sweep_nn (same size, stroke_width and DSVG_RASTER_FILL) and dout
+ *    fp32 [B, size, size] -> dsegs fp32 [B, cap, 4] (16-byte aligned): the gradient with respect to the VERTICES (ax, ay, bx,
+ *    by) of every record - with respect to b, not to the stored difference b - a.  Rows below seg_counts[b] are all written,
+ *    rows past it are not.  A gather: a group of 16 lanes (DSVG_RASTER_WIDE: of 64) per record walks the record's bounding
+ *    box dilated by the culling reach in a fixed order; no atomics, bit-reproducible.
+ *  raster_segments_bwd: the transpose of raster_segments (linear in args, so the fp32 commands are all it needs): dsegs and
+ *    seg_counts as above, built with the same G, L, n, fill -> dargs fp32 [B*G, L, 11], every element written.  Vertex 0 of a
+ *    command is the end position (args 9:11) of the row before it whatever that row holds (the constant (0, 0) on row 0: no
+ *    gradient), vertex n - 1 the row's own; interior vertices carry the Bernstein weights (`c`) or ((n - 1 - q), q) / (n - 1)
+ *    (`l`); a closing chord's a is its last row's end position, its b the sub-path's start point.  Columns 0-4, padding and
+ *    rows that neither draw nor precede a drawing row get exact zeros.  Limits as raster_segments. */
+#define DSVG_RASTER_WIDE 4
+int dsvg_raster_sweep_nn(const void* segs, const int32_t* seg_counts, int64_t B, int64_t cap, int32_t size, float stroke_width,
+                         int32_t flags, float* out, int32_t* idx, void* stream);
+int dsvg_raster_sweep_bwd(const void* segs, const int32_t* seg_counts, const float* out, const int32_t* idx, const float* dout,
+                          int64_t B, int64_t cap, int32_t size, float stroke_width, int32_t flags, float* dsegs, void* stream);
+int dsvg_raster_segments_bwd(const float* commands, const float* dsegs, const int32_t* seg_counts, int64_t B, int32_t G,
+                             int32_t L, int32_t n, int32_t fill, float* dargs, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The argument head fused with its consumers (csrc/head_fused.hip): args_fcn = Linear(256 -> n_args *
