@@ -8,14 +8,20 @@
 // One workgroup of 8 waves per (column block c, row slice z), 8 x nsplit workgroups, all column blocks of a slice on one
 // XCD (workgroup b runs on XCD b % 8) so that the slice's dym rows are fetched into that XCD's L2 once.  The workgroup walks
 // its slice in 64-row tiles; a tile = dym [64][256] (two [64][128] images, 256-byte rows) + hp[:, c] [64][64] (128-byte
-// rows), 40 KiB, LDS-DMA'd by all 8 waves into a 3-slot ring (two tiles in flight beside the one consumed); W2p[:, c]
-// ([256][64], 32 KiB) is requested up front and stays.  152 KiB of LDS, one workgroup per CU.
-//   waves 0-3: dpre - one 32x32 tile each (K = 256: dym rows by ds_read_b128, W2p columns by ds_read_b64_tr_b16), the same
-//              MFMA sequence, operand order and epilogue as the EPI_GATE GEMM (bit-identical dpre); the gate is read from the
-//              staged hp image instead of global memory.
+// rows), 40 KiB, LDS-DMA'd by all 8 waves into a 4-slot ring (three tiles in flight beside the one consumed): 160 KiB, all
+// of the CU's LDS, one workgroup per CU.  W2p[:, c] ([256][64], 32 KiB) is row-invariant and read by the dpre waves only: it
+// is requested up front into the ring's last slot, each dpre wave takes its 16 fragments (64 registers per lane) out of it
+// once, and the slot then joins the ring.
+//   waves 0-3: dpre - one 32x32 tile each (K = 256: dym rows by ds_read_b128, W2p columns by ds_read_b64_tr_b16, once), the
+//              same MFMA sequence, operand order and epilogue as the EPI_GATE GEMM (bit-identical dpre); the gate is read from
+//              the staged hp image instead of global memory.
 //   waves 4-7: G2p - 64 dym features x the 64 columns each, accumulated across all tiles of the slice (both operands by
 //              ds_read_b64_tr_b16 from the same images), + db2's row sums; the slice is written like the split-K GEMM's
 //              (same slices, same per-slice order: bit-identical partials) and reduced by the deferred funnel.
+// Every wave issues 5 of a tile's 40 DMA pieces and counts them (vmcnt).  The dpre waves' stores sit in the same counter and
+// do not return in order with the loads, so their wait can only be longer than needed, never shorter.  Letting the four G2p
+// waves, which store nothing inside the loop, issue all 40 pieces behind an exact count was measured and is slower (35.9
+// against 31.2 us at 41,216 rows, 58.8 against 58.0 at 63,488: profiles/ffn_gate_dw2_ring_ab.log).
 // Images: 256-byte rows: 16-byte chunk ch of row r at ch ^ (((r & 3) << 2) | ((r >> 2) & 3)) - conflict-free for the row
 // reads and the transposed reads alike; 128-byte rows (read transposed only): ch ^ (((r >> 1) & 1) << 2).
 // Rows past the slice's end (ragged row count, clamped on the load side) are zeroed in the G2p operand and not stored.
@@ -29,9 +35,11 @@ constexpr int GT = 64;                       // token rows per tile
 constexpr int W2_BYTES = 256 * 64 * 2;       // W2p[:, c] image
 constexpr int SLOT = (2 * 64 * 128 + 64 * 64) * 2;     // dym images + hp image of one tile (40 KiB)
 constexpr int HP_OFF = 2 * 64 * 128 * 2;     // hp image inside a slot
-constexpr int NSLOT = 3;
-constexpr int LDS_BYTES = W2_BYTES + NSLOT * SLOT;
+constexpr int NSLOT = 4;
+constexpr int W2_AT = (NSLOT - 1) * SLOT;    // the W2p image lands in the last slot, which tile NSLOT - 1 overwrites
+constexpr int LDS_BYTES = NSLOT * SLOT;
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget of a CU");
+static_assert(W2_BYTES <= SLOT, "the W2p image fits a slot");
 
 __device__ __forceinline__ int sw256(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
 __device__ __forceinline__ int sw128(int r) { return ((r >> 1) & 1) << 2; }
@@ -157,9 +165,18 @@ __global__ __launch_bounds__(512, 1) void ffn_gate_dw2_kernel(const bf16_t* __re
         const char* a[5];
 #pragma unroll
         for (int i = 0; i < 5; ++i) a[i] = src[i] + (size_t)min(r0 + srow[i], T - 1) * sld[i];
-        const uint32_t dst = __builtin_amdgcn_readfirstlane(lds0 + W2_BYTES + (uint32_t)(s % NSLOT) * SLOT + (uint32_t)wave * 5 * 1024);
+        const uint32_t dst = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(s % NSLOT) * SLOT + (uint32_t)wave * 5 * 1024);
         dma5(a[0], a[1], a[2], a[3], a[4], dst);
     };
+    // the wave's pieces of tile s landed: the tiles issued after it (up to NSLOT - 2 at this point) may stay in flight, 5
+    // DMAs each (the dpre stores issued since only make this wait longer)
+    auto wait_tile = [&](int s) {
+        const int ahead = min(NSLOT - 2, n_tiles - 1 - s);
+        if (ahead >= 2) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
+        else if (ahead == 1) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    };
+    static_assert(NSLOT == 4, "wait_tile counts for a 4-slot ring");
 
     // ---- fragment offsets --------------------------------------------------------------------------------------------
     const int g = lane >> 4, q = lane & 15, qq = q >> 2, pp = q & 3;
@@ -192,90 +209,95 @@ __global__ __launch_bounds__(512, 1) void ffn_gate_dw2_kernel(const bf16_t* __re
     const bool do_rs = !p1 && c == 0;
     float rsa0 = 0.f, rsa1 = 0.f, rsb0 = 0.f, rsb1 = 0.f;
 
-    auto compute = [&](int s) {
-        const char* slot = lds + W2_BYTES + (s % NSLOT) * SLOT;
+    // dpre waves: the wave's 16 W2p fragments (columns 32 wn .., k steps kk), read once from the image in the last slot
+    Frag8 w2f[16];
+
+    auto dpre_tile = [&](int s) {
+        const char* slot = lds + (s % NSLOT) * SLOT;
         const int r0 = row_begin + s * GT;
-        if (p1) {
-            // dpre tile: acc = sum over kk of mfma(W2p columns, dym rows) - EPI_GATE's operand order and k order
-            floatx16 acc;
+        // dpre tile: acc = sum over kk of mfma(W2p columns, dym rows) - EPI_GATE's operand order and k order
+        floatx16 acc;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
-            for (int kk = 0; kk < 16; ++kk) {
-                Frag8 a;
-                a.u = *reinterpret_cast<const uint4*>(slot + (kk >> 3) * 16384 + pr * 256 +
-                                                      16 * ((2 * (kk & 7) + h) ^ sw256(pr)));
-                const bf16x8 b = ld_tr(lds, w2_off + kk * 2048, w2_off + kk * 2048 + 512);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b, a.v, acc, 0, 0, 0);
-            }
-            // epilogue (gemm_bf16_glds.hip tile16, EPI_GATE): 16 consecutive columns of token row m per lane
-            uint32_t x[4][4];
+        for (int kk = 0; kk < 16; ++kk) {
+            Frag8 a;
+            a.u = *reinterpret_cast<const uint4*>(slot + (kk >> 3) * 16384 + pr * 256 +
+                                                  16 * ((2 * (kk & 7) + h) ^ sw256(pr)));
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2f[kk].v, a.v, acc, 0, 0, 0);
+        }
+        // epilogue (gemm_bf16_glds.hip tile16, EPI_GATE): 16 consecutive columns of token row m per lane
+        uint32_t x[4][4];
 #pragma unroll
-            for (int gq = 0; gq < 4; ++gq)
+        for (int gq = 0; gq < 4; ++gq)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) x[gq][e] = __float_as_uint(acc[4 * gq + e]);
+            for (int e = 0; e < 4; ++e) x[gq][e] = __float_as_uint(acc[4 * gq + e]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            auto s01 = __builtin_amdgcn_permlane32_swap(x[0][e], x[1][e], false, false);
+            auto s23 = __builtin_amdgcn_permlane32_swap(x[2][e], x[3][e], false, false);
+            x[0][e] = s01[0]; x[1][e] = s01[1]; x[2][e] = s23[0]; x[3][e] = s23[1];
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            auto s02 = __builtin_amdgcn_permlane32_swap(x[0][e], x[2][e], false, false);
+            auto s13 = __builtin_amdgcn_permlane32_swap(x[1][e], x[3][e], false, false);
+            x[0][e] = s02[0]; x[2][e] = s02[1]; x[1][e] = s13[0]; x[3][e] = s13[1];
+        }
+        uint4 pk[2];
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) {
+            float v[8];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { v[e] = __uint_as_float(x[2 * cb][e]); v[4 + e] = __uint_as_float(x[2 * cb + 1][e]); }
+            const uint4 gt = *reinterpret_cast<const uint4*>(slot + HP_OFF + pr * 128 +
+                                                             16 * ((4 * wn + 2 * h + cb) ^ sw128(pr)));
+            const uint32_t gw[4] = {gt.x, gt.y, gt.z, gt.w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                auto s01 = __builtin_amdgcn_permlane32_swap(x[0][e], x[1][e], false, false);
-                auto s23 = __builtin_amdgcn_permlane32_swap(x[2][e], x[3][e], false, false);
-                x[0][e] = s01[0]; x[1][e] = s01[1]; x[2][e] = s23[0]; x[3][e] = s23[1];
+                const float g0 = __uint_as_float(gw[e] << 16), g1 = __uint_as_float(gw[e] & 0xffff0000u);
+                v[2 * e] = g0 > 0.f ? v[2 * e] * gate_scale : 0.f;
+                v[2 * e + 1] = g1 > 0.f ? v[2 * e + 1] * gate_scale : 0.f;
             }
+            pk[cb] = make_uint4(f2bf_pk(v[0], v[1]), f2bf_pk(v[2], v[3]), f2bf_pk(v[4], v[5]), f2bf_pk(v[6], v[7]));
+        }
+        const int m = r0 + pr;
+        if (m < row_end) {
+            bf16_t* cp = dpre + (size_t)m * 512 + 64 * c + 32 * wn + 16 * h;
+            *reinterpret_cast<uint4*>(cp) = pk[0];
+            *reinterpret_cast<uint4*>(cp + 8) = pk[1];
+        }
+    };
+    auto g2p_tile = [&](int s) {
+        const char* slot = lds + (s % NSLOT) * SLOT;
+        const int r0 = row_begin + s * GT;
+        const bool ragged = r0 + GT > row_end;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                auto s02 = __builtin_amdgcn_permlane32_swap(x[0][e], x[2][e], false, false);
-                auto s13 = __builtin_amdgcn_permlane32_swap(x[1][e], x[3][e], false, false);
-                x[0][e] = s02[0]; x[2][e] = s02[1]; x[1][e] = s13[0]; x[3][e] = s13[1];
+        for (int kk = 0; kk < 4; ++kk) {
+            bf16x8 a0 = ld_tr(slot, da_off[0][0] + kk * 4096, da_off[0][1] + kk * 4096);
+            bf16x8 a1 = ld_tr(slot, da_off[1][0] + kk * 4096, da_off[1][1] + kk * 4096);
+            const bf16x8 b0 = ld_tr(slot, hb_off[0] + kk * 2048, hb_off[0] + kk * 2048 + 512);
+            const bf16x8 b1 = ld_tr(slot, hb_off[1] + kk * 2048, hb_off[1] + kk * 2048 + 512);
+            if (ragged) {
+                const int lim = row_end - (r0 + 16 * kk + 8 * h);
+                a0 = zero_from(a0, lim);
+                a1 = zero_from(a1, lim);
             }
-            uint4 pk[2];
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb) {
-                float v[8];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { v[e] = __uint_as_float(x[2 * cb][e]); v[4 + e] = __uint_as_float(x[2 * cb + 1][e]); }
-                const uint4 gt = *reinterpret_cast<const uint4*>(slot + HP_OFF + pr * 128 +
-                                                                 16 * ((4 * wn + 2 * h + cb) ^ sw128(pr)));
-                const uint32_t gw[4] = {gt.x, gt.y, gt.z, gt.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float g0 = __uint_as_float(gw[e] << 16), g1 = __uint_as_float(gw[e] & 0xffff0000u);
-                    v[2 * e] = g0 > 0.f ? v[2 * e] * gate_scale : 0.f;
-                    v[2 * e + 1] = g1 > 0.f ? v[2 * e + 1] * gate_scale : 0.f;
-                }
-                pk[cb] = make_uint4(f2bf_pk(v[0], v[1]), f2bf_pk(v[2], v[3]), f2bf_pk(v[4], v[5]), f2bf_pk(v[6], v[7]));
-            }
-            const int m = r0 + pr;
-            if (m < row_end) {
-                bf16_t* cp = dpre + (size_t)m * 512 + 64 * c + 32 * wn + 16 * h;
-                *reinterpret_cast<uint4*>(cp) = pk[0];
-                *reinterpret_cast<uint4*>(cp + 8) = pk[1];
-            }
-        } else {
-            const bool ragged = r0 + GT > row_end;
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                bf16x8 a0 = ld_tr(slot, da_off[0][0] + kk * 4096, da_off[0][1] + kk * 4096);
-                bf16x8 a1 = ld_tr(slot, da_off[1][0] + kk * 4096, da_off[1][1] + kk * 4096);
-                const bf16x8 b0 = ld_tr(slot, hb_off[0] + kk * 2048, hb_off[0] + kk * 2048 + 512);
-                const bf16x8 b1 = ld_tr(slot, hb_off[1] + kk * 2048, hb_off[1] + kk * 2048 + 512);
-                if (ragged) {
-                    const int lim = row_end - (r0 + 16 * kk + 8 * h);
-                    a0 = zero_from(a0, lim);
-                    a1 = zero_from(a1, lim);
-                }
-                acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a0, acc00, 0, 0, 0);
-                acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a1, acc01, 0, 0, 0);
-                acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a0, acc10, 0, 0, 0);
-                acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a1, acc11, 0, 0, 0);
-                if (do_rs) {
-                    if (kk < 2) { rsa0 = rowsum8(a0, rsa0); rsa1 = rowsum8(a1, rsa1); }
-                    else { rsb0 = rowsum8(a0, rsb0); rsb1 = rowsum8(a1, rsb1); }
-                }
+            acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a0, acc00, 0, 0, 0);
+            acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a1, acc01, 0, 0, 0);
+            acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a0, acc10, 0, 0, 0);
+            acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a1, acc11, 0, 0, 0);
+            if (do_rs) {
+                if (kk < 2) { rsa0 = rowsum8(a0, rsa0); rsa1 = rowsum8(a1, rsa1); }
+                else { rsb0 = rowsum8(a0, rsb0); rsb1 = rowsum8(a1, rsb1); }
             }
         }
     };
 
+    // DMA order of every wave: tile 0, the W2p image, tiles 1 .. NSLOT - 2, then one tile per iteration
     if (n_tiles > 0) {
-        // W2p[:, c] up front: wave w fills pieces 4 w .. 4 w + 3 of the [256][64] image
+        issue(0);
+        // W2p[:, c] into the last slot: wave w fills pieces 4 w .. 4 w + 3 of the [256][64] image
         const char* a[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -283,18 +305,34 @@ __global__ __launch_bounds__(512, 1) void ffn_gate_dw2_kernel(const bf16_t* __re
             const int ch = (lane & 7) ^ sw128(r);
             a[i] = (const char*)w2p + ((size_t)r * 512 + 64 * c + 8 * ch) * 2;
         }
-        dma4(a[0], a[1], a[2], a[3], __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)wave * 4 * 1024));
+        dma4(a[0], a[1], a[2], a[3], __builtin_amdgcn_readfirstlane(lds0 + W2_AT + (uint32_t)wave * 4 * 1024));
+        for (int s = 1; s < NSLOT - 1 && s < n_tiles; ++s) issue(s);
+        wait_tile(0);                       // tile 0 and, issued before tile 1, the W2p image
+        __builtin_amdgcn_s_barrier();       // the W2p image landed everywhere
     }
-    for (int s = 0; s < 2 && s < n_tiles; ++s) issue(s);
+    // One loop per role: in a common loop the dpre waves' 64 fragment registers and the G2p waves' 64 accumulators are live
+    // together and the kernel spills inside the loop.  Both loops pass the same barriers.
+    if (p1) {
+        if (n_tiles > 0) {
+#pragma unroll
+            for (int kk = 0; kk < 16; ++kk) w2f[kk].v = ld_tr(lds + W2_AT, w2_off + kk * 2048, w2_off + kk * 2048 + 512);
+            // in registers before the loop's first barrier hands the slot to tile NSLOT - 1
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        }
+        for (int s = 0; s < n_tiles; ++s) {
+            wait_tile(s);
+            __builtin_amdgcn_s_barrier();   // (as in the G2p waves' loop below)
+            if (s + NSLOT - 1 < n_tiles) issue(s + NSLOT - 1);
+            dpre_tile(s);
+        }
+        return;
+    }
     for (int s = 0; s < n_tiles; ++s) {
-        // tile s landed (5 DMA instructions per tile and wave; the dpre stores issued since only make this wait longer)
-        if (s + 1 < n_tiles) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_tile(s);
         __builtin_amdgcn_s_barrier();       // tile s landed everywhere; everybody is done with tile s - 1's slot
-        if (s + 2 < n_tiles) issue(s + 2);
-        compute(s);
+        if (s + NSLOT - 1 < n_tiles) issue(s + NSLOT - 1);
+        g2p_tile(s);
     }
-    if (p1) return;
 
     // ---- G2p slice z: rows = dym features (64 ww + 32 it + (lane & 31)), columns 64 c + 32 jn + ... -------------------
     const size_t slice = dsvg_splitk_slice(256, 512, true);
