@@ -36,8 +36,8 @@ extern "C" {
  * 3: dsvg_latent_chain_fwd / dsvg_latent_chain_bwd added.  4: seq_add_ld argument of dsvg_attn_block_fwd / dsvg_gs_layer_fwd.
  * 5 (round 5): dsvg_sample_rows / dsvg_head_sample (categorical sampling on the device), dsvg_layernorm_bwd_masked added.
  * 6: dsvg_pack_images, dsvg_defer_zero added; dg argument of dsvg_gs_layer_bwd.
- * 7 (round 6): dsvg_attn_bwd_dx added; a layer of dsvg_attn_pack_bwd grew from 128 to 512 fragments (in_proj_weight^T behind
- *    out_proj.weight^T).
+ * 7 (round 6): the one-launch attention input gradient added (removed in 18); a layer of dsvg_attn_pack_bwd grew from 128 to
+ *    512 fragments (in_proj_weight^T behind out_proj.weight^T).
  * 8 (round 6): dsvg_gs_stack_fwd / dsvg_gs_stack_bwd added (one launch per STACK of group-stage layers).
  * 9 (round 6): dg_ld argument of dsvg_bcast_add_bwd / dsvg_bcast_add_bwd_masked (dg as a column block of a wider buffer).
  * 10: dsvg_ffn_gate_dw2 added (the gated dpre GEMM and the dW2 split-K GEMM of the fused FFN backward as one launch).
@@ -49,8 +49,11 @@ extern "C" {
  * 15: dsvg_emd (+ dsvg_emd_workspace_bytes) / dsvg_emd_bwd / dsvg_polyline_length / dsvg_polyline_length_bwd added (the ordered
  *     point loss and the length losses of deepsvg/difflib/loss.py).
  * 16: dsvg_raster_segments (+ dsvg_raster_workspace_bytes) / dsvg_raster_sweep added (images of a decoded batch).
- * 17: dsvg_raster_sweep_nn / dsvg_raster_sweep_bwd / dsvg_raster_segments_bwd added (the gradient of an image). */
-#define DSVG_ABI_VERSION 17
+ * 17: dsvg_raster_sweep_nn / dsvg_raster_sweep_bwd / dsvg_raster_segments_bwd added (the gradient of an image).
+ * 18: the one-launch attention input gradient of version 7 removed: its entry point, its workspace query and its debug clock
+ *     (opt-in since round 6, never ahead of the two launches it replaced); a layer of dsvg_attn_pack_bwd is back to 128
+ *     fragments (out_proj.weight^T only). */
+#define DSVG_ABI_VERSION 18
 
 const char* dsvg_last_error(void);
 int dsvg_version(void);
@@ -378,31 +381,12 @@ int dsvg_attention_causal_fwd(int32_t dtype, const void* qkv, const uint64_t* ke
  * dO = dx1m . Wo is formed per tile on chip: replaces the `dao = dx1m @ out_proj.weight` GEMM launch (its 512 B / token
  * written and re-read) in front of dsvg_attention_bwd (autograd of layers/functional.py:248-249 + :197-247).
  * dsvg_attn_pack_bwd: offs[layer][1] = element offset of out_proj.weight in flat_f32 (the offs table of dsvg_attn_pack);
- * packed_bwd: dsvg_attn_pack_bwd_elems(n_layers) bf16 elements (512 x 512 per layer: 128 fragments of out_proj.weight^T, then
- * 384 fragments of in_proj_weight^T for dsvg_attn_bwd_dx; offs[layer][0] = element offset of in_proj_weight). */
+ * packed_bwd: dsvg_attn_pack_bwd_elems(n_layers) bf16 elements (128 x 512 per layer: the 128 fragments [head 8][K step 16] of
+ * out_proj.weight^T; offs[layer][0] is not read). */
 int dsvg_attention_bwd_outproj(const void* qkv, const uint64_t* key_mask, const int32_t* seq_off, int64_t total_rows,
                                const int32_t* tile_first, const void* dx1m, const void* wo_packed_bwd, void* dqkv,
                                int64_t n_seq, int32_t S, float scale, float drop_p, uint32_t drop_site,
                                const uint64_t* seed, void* stream);
-/* Input gradient of the attention sub-block in ONE launch (bf16, d_model 256; csrc/attn_bwd_dx.hip):
- *     dx = res + LayerNorm'( dqkv . in_proj_weight ),   dgamma = sum_t dxn1 * xh,   dbeta = sum_t dxn1
- * with dxn1 = dqkv . in_proj_weight [rows, 256] never written: replaces the input-gradient dsvg_gemm behind dsvg_attention_bwd
- * / dsvg_attention_bwd_outproj and the dsvg_layernorm_bwd (_masked) of norm1 behind it - autograd of
- * deepsvg/model/layers/improved_transformer.py:43-45 / :127-129 (norm1 + in_proj of layers/functional.py:92).
- * dqkv [rows, 768], x / res / dx [rows, 256] bf16 row-major; mean / rstd: the statistics dsvg_attn_block_fwd /
- * dsvg_layernorm_fwd stored; gamma fp32 [256]; packed_bwd_layer: one layer of dsvg_attn_pack_bwd (fragments 128 .. 511 =
- * in_proj_weight^T); dgamma / dbeta fp32 [256], written (accumulate = 0) or added to, through the deterministic partial
- * reduction (queued inside a dsvg_defer_scope); workspace: dsvg_attn_bwd_dx_workspace_bytes(rows).
- * dx_masked (optional): second output = dsvg_drop_apply(dx, drop_p, drop_site) as in dsvg_layernorm_bwd_masked. */
-int64_t dsvg_attn_bwd_dx_workspace_bytes(int64_t rows);
-/* development probe of dsvg_attn_bwd_dx: buf = device buffer of (workgroups x 4 waves x 8) uint64 stamps of the 100 MHz
- * counter (wave start, first rows staged, K loop done, pass 1 done, sums published, stores issued) or NULL (off);
- * scripts/attn_bwd_dx_probe.py */
-int dsvg_attn_bwd_dx_debug_clock(void* buf);
-int dsvg_attn_bwd_dx(const void* dqkv, const void* x, const float* mean, const float* rstd, const float* gamma,
-                     const void* res, const void* packed_bwd_layer, void* dx, float* dgamma, float* dbeta,
-                     int32_t accumulate, int64_t rows, float* workspace, int64_t workspace_bytes, void* dx_masked,
-                     float drop_p, uint32_t drop_site, const void* seed, void* stream);
 int64_t dsvg_attn_pack_bwd_elems(int32_t n_layers);
 int dsvg_attn_pack_bwd(const float* flat_f32, const int64_t* offs, int32_t n_layers, void* packed_bwd, void* stream);
 int dsvg_attention_causal_bwd(int32_t dtype, const void* qkv, const uint64_t* key_mask, const void* dout, void* dqkv,

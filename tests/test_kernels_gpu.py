@@ -1135,72 +1135,6 @@ def test_ffn_bwd_dx_masked_second_output(gpu_device):
     assert torch.equal(dx2, dx0) and dxm2 is dx2
 
 
-@pytest.mark.parametrize("rows", [128, 4133, 40001, 63488])
-@pytest.mark.parametrize("masked", [False, True])
-def test_attn_bwd_dx_matches_the_two_launches_and_fp32(gpu_device, rows, masked):
-    """dsvg_attn_bwd_dx (round 6: dx = res + LayerNorm'(dqkv . W_in), dgamma, dbeta in one launch) against
-    (a) the fp32 torch restatement of the same math on the same bf16 inputs - dx within one bf16 rounding of the fp32 result
-        (2^-8 of the row's scale), dgamma / dbeta 1e-4 relative to the vector's largest entry (fp32 sums in another order);
-    (b) the two launches it replaces, dsvg_gemm + dsvg_layernorm_bwd: those round the intermediate dxn1 to bf16, the fused
-        kernel does not, so (b) bounds the DIFFERENCE by bf16 rounding of the intermediate: 1.2e-2 of the scale;
-    (c) the masked second output bit-identical to dsvg_drop_apply of the first."""
-    flat, offs, prm = _attn_setup(seed=17)
-    layer = 1
-    oi = int(offs[layer][0])
-    win = flat[oi:oi + 768 * 256].view(768, 256).to(torch.bfloat16)
-    img = ops.attn_pack_bwd(flat, offs, 2)
-    wib = img[layer * ops.ATTN_BWD_LAYER_ELEMS:(layer + 1) * ops.ATTN_BWD_LAYER_ELEMS]
-    eimg = R.attn_pack_bwd(flat, offs, 2)
-    assert torch.equal(eimg[layer * R.ATTN_BWD_LAYER_ELEMS:(layer + 1) * R.ATTN_BWD_LAYER_ELEMS][65536:].view(768, 256), win)
-    x = (_rand(rows, 256, seed=41) * 1.3 + 0.2).to(torch.bfloat16)
-    dqkv = (_rand(rows, 768, seed=42) * 0.4).to(torch.bfloat16)
-    res = _rand(rows, 256, seed=43).to(torch.bfloat16)
-    gamma = (1.0 + 0.2 * _rand(256, seed=44)).contiguous()
-    beta = (0.1 * _rand(256, seed=45)).contiguous()
-    _, mean, rstd = ops.layernorm_fwd(x, gamma, beta)
-    seed = _seed_tensor(0x0DDBA11C0FFEE123)
-    mk = (0.1, 91, seed) if masked else None
-    out = ops.attn_bwd_dx(dqkv, x, mean, rstd, gamma, res, wib, masked=mk)
-    dx, dg, db = out[:3]
-    # (a) fp32 restatement
-    want = R.layernorm_bwd(dqkv.float() @ win.float(), x.float(), mean, rstd, gamma, res=res.float())
-    _close(dx, want[0], 2.0 ** -8, "dx vs fp32")
-    _close(dg, want[1], 1e-4, "dgamma vs fp32")
-    _close(db, want[2], 1e-4, "dbeta vs fp32")
-    # (b) the two launches of round 5
-    dxn1 = ops.gemm(dqkv, win, b_kc=False)
-    two = ops.layernorm_bwd(dxn1, x, mean, rstd, gamma, res=res)
-    _close(dx, two[0], 1.2e-2, "dx vs gemm + layernorm_bwd")
-    _close(dg, two[1], 1.2e-2, "dgamma vs gemm + layernorm_bwd")
-    _close(db, two[2], 1.2e-2, "dbeta vs gemm + layernorm_bwd")
-    if masked:
-        assert torch.equal(out[3], ops.drop_apply(dx, 0.1, 91, seed))
-        assert 0.05 < (out[3] == 0).float().mean().item() < 0.15
-    # accumulate = True adds to what is there; a caller-provided dx buffer (a row prefix of a larger tensor) is written in place
-    big = torch.zeros(rows + 7, 256, dtype=torch.bfloat16, device=DEV)
-    dg2, db2 = dg.clone(), db.clone()
-    out2 = ops.attn_bwd_dx(dqkv, x, mean, rstd, gamma, res, wib, dx=big[:rows], dgamma=dg2, dbeta=db2, accumulate=True)
-    assert out2[0].data_ptr() == big.data_ptr() and torch.equal(big[:rows], dx) and not big[rows:].any()
-    _close(dg2, 2 * dg, 1e-6, "accumulated dgamma")
-    _close(db2, 2 * db, 1e-6, "accumulated dbeta")
-
-
-def test_attn_bwd_dx_is_bit_reproducible(gpu_device):
-    """no atomics, fixed-order sums: two launches on the same inputs give the same bits (dx and the parameter gradients)"""
-    flat, offs, prm = _attn_setup(seed=3)
-    img = ops.attn_pack_bwd(flat, offs, 2)
-    wib = img[:ops.ATTN_BWD_LAYER_ELEMS]
-    rows = 20000
-    x = _rand(rows, 256, seed=1).to(torch.bfloat16)
-    dqkv = _rand(rows, 768, seed=2).to(torch.bfloat16)
-    res = _rand(rows, 256, seed=3).to(torch.bfloat16)
-    gamma = (1.0 + 0.1 * _rand(256, seed=4)).contiguous()
-    _, mean, rstd = ops.layernorm_fwd(x, gamma, torch.zeros_like(gamma))
-    a = ops.attn_bwd_dx(dqkv, x, mean, rstd, gamma, res, wib)
-    b = ops.attn_bwd_dx(dqkv, x, mean, rstd, gamma, res, wib)
-    assert all(torch.equal(u, v) for u, v in zip(a, b))
-
-
 def test_ffn_wgrad_finish_and_full_gradients(gpu_device):
     """fused forward + backward + the two weight-gradient GEMMs + wgrad_finish against autograd on the unfused fp32
     formulation (LayerNorm with gamma / beta, linear1, ReLU, linear2, residual; no dropout): dx, dW1, db1, dW2, db2,
@@ -1328,6 +1262,28 @@ def test_attn_pack_layout(gpu_device):
             r = 8 * ks2 + e
             col = 32 * h + (r & 3) + 8 * (r >> 2) + 4 * half
             assert torch.equal(img[layer, f], Wo[32 * t + i, col]), f
+
+
+def test_attn_pack_bwd_layout(gpu_device):
+    """every element of the attention backward image, bit for bit, against the index formula of csrc/pack_images.h:
+    img[layer][head h][K step ks][lane l][e] = bf16(Wo[16 ks + 8 (l >> 5) + e][32 h + (l & 31)]), 128 fragments per layer, in
+    a caller-provided buffer, and nothing written behind the last layer"""
+    flat, offs, _ = _attn_setup(seed=6)
+    n = 2 * ops.ATTN_BWD_LAYER_ELEMS
+    assert ops.ATTN_BWD_LAYER_ELEMS == 128 * 512
+    tail = (torch.arange(512, dtype=torch.int16) + 0x3C00).view(torch.bfloat16).to(DEV)
+    buf = torch.zeros(n + 512, dtype=torch.bfloat16, device=DEV)
+    buf[n:] = tail
+    out = ops.attn_pack_bwd(flat, offs, 2, buf[:n])
+    assert out.data_ptr() == buf.data_ptr()
+    img = buf[:n].view(2, 8, 16, 64, 8).view(torch.int16).cpu()
+    lane = torch.arange(64).view(1, 1, 64, 1)
+    h, ks, e = torch.arange(8).view(8, 1, 1, 1), torch.arange(16).view(1, 16, 1, 1), torch.arange(8).view(1, 1, 1, 8)
+    for layer in range(2):
+        oo = int(offs[layer][1])
+        Wo = flat[oo:oo + 65536].view(256, 256).to(torch.bfloat16).view(torch.int16).cpu()
+        assert torch.equal(img[layer], Wo[16 * ks + 8 * (lane >> 5) + e, 32 * h + (lane & 31)]), layer
+    assert torch.equal(buf[n:].view(torch.int16), tail.view(torch.int16))
 
 
 def _attn_case(kind, seed):
