@@ -7,6 +7,7 @@ Public surface mirrors the reference (alexandre01/deepsvg):
     deepsvg_amd.metrics         <->  deepsvg.difflib: SVGTensor.sample_points + chamfer_loss (reconstruction error)
                                      and the other losses of difflib/loss.py: svg_emd_loss, svg_length_loss, continuity_loss
     deepsvg_amd.render          <->  deepsvg.svglib: SVG.draw of a decoded batch (stroke / fill coverage images, interpolation)
+    deepsvg_amd.paths           <->  deepsvg.svglib: SVG.canonicalize + numericalize of a batch (the form the encoder was trained on)
 """
 # (No process-wide side effects on import.  The data-parallel hipGraph step wants GPU_MAX_HW_QUEUES=6 in the environment BEFORE
 # the HIP runtime comes up - see trainer.HW_QUEUES_NOTE; bench.py sets it, TrainStep warns when a data-parallel trainer
@@ -17,6 +18,7 @@ from .model import SVGTransformer  # noqa: F401
 from .loss import SVGLoss  # noqa: F401
 from . import metrics  # noqa: F401
 from . import render  # noqa: F401
+from . import paths  # noqa: F401
 
 __all__ = ["SVGTransformer", "SVGLoss", "_DefaultConfig", "Hierarchical", "HierarchicalOrdered", "OneStageOneShot", "metrics",
-           "render"]
+           "render", "paths"]

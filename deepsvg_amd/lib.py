@@ -12,12 +12,13 @@ LIB_PATH = os.path.join(_HERE, "_lib", "libdsvg_hip.so")
 
 DSVG_F32 = 0
 DSVG_BF16 = 1
-DSVG_I64 = 2          # input dtype of dsvg_sample_points / dsvg_raster_segments only
+DSVG_I64 = 2          # input dtype of dsvg_sample_points / dsvg_raster_segments / dsvg_canonicalize only
+DSVG_PATHS_GROUPED, DSVG_PATHS_CONCAT = 0, 1   # layouts of dsvg_canonicalize
 DSVG_RASTER_FILL, DSVG_RASTER_CULL = 1, 2      # flags of dsvg_raster_sweep
 DSVG_RASTER_WIDE = 4                           # flag of dsvg_raster_sweep_bwd: a wave per chord, not 16 lanes
 # == DSVG_ABI_VERSION of include/dsvg.h at the time SIGNATURES below was written: load() refuses a library built from another
 # header (a stale .so with the old argument lists would otherwise be called with a stream where a size is expected)
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 c_i32, c_i64, c_u32, c_f32 = C.c_int32, C.c_int64, C.c_uint32, C.c_float
 vp = C.c_void_p
@@ -171,6 +172,7 @@ SIGNATURES = {
     "dsvg_raster_sweep_nn": (c_i32, [vp, vp, c_i64, c_i64, c_i32, c_f32, c_i32, vp, vp, vp]),
     "dsvg_raster_sweep_bwd": (c_i32, [vp, vp, vp, vp, vp, c_i64, c_i64, c_i32, c_f32, c_i32, vp, vp]),
     "dsvg_raster_segments_bwd": (c_i32, [vp, vp, vp, c_i64, c_i32, c_i32, c_i32, c_i32, vp, vp]),
+    "dsvg_canonicalize": (c_i32, [c_i32, vp, vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dsvg_ffn_pack_bytes": (c_i64, [c_i32, c_i32]),
     "dsvg_ffn_pack": (c_i32, [vp, vp, c_i32, c_i32, c_i32, vp, vp, vp, vp, vp]),
     "dsvg_ffn_fwd": (c_i32, [vp, vp, vp, vp, vp, vp, vp, vp, c_i64, c_f32, c_f32, c_u32, c_u32, vp, c_i32, vp]),

@@ -1428,6 +1428,38 @@ def raster_segments_bwd(commands, dsegs, seg_counts, n=10, groups=1, fill=False)
 
 
 # ------------------------------------------------------------------------------------------------
+# canonical path order of a batch (svglib/svg.py:333-349 on the tensors themselves; csrc/paths.hip)
+# ------------------------------------------------------------------------------------------------
+def canonicalize(commands, args, g_out, s_out, concat=False, numericalize=0):
+    """commands [N, G, S] / args [N, G, S, 11], both float32 or both int64, G * S <= 2048 -> the dict of
+    deepsvg_amd.paths.canonicalize: "commands" [N, g_out, s_out] (concat: [N, s_out]) and "args" (..., 11) in the input dtype,
+    "n_groups" int32 [N], "len_groups" / "source_group" int32 [N, g_out], "reversed" bool [N, g_out], "valid" bool [N].
+    One launch, no workspace; include/dsvg.h has the definition"""
+    _chk(commands, args)
+    assert commands.dim() == 3 and args.dim() == 4 and args.shape[:3] == commands.shape and args.shape[3] == 11
+    assert commands.dtype == args.dtype and commands.dtype in (torch.float32, torch.int64)
+    assert commands.is_contiguous() and args.is_contiguous()
+    N, G, S = commands.shape
+    dev = commands.device
+    rows = (int(s_out),) if concat else (int(g_out), int(s_out))
+    out_c = torch.empty((N,) + rows, dtype=commands.dtype, device=dev)
+    out_a = torch.empty((N,) + rows + (11,), dtype=commands.dtype, device=dev)
+    n_groups = torch.empty(N, dtype=torch.int32, device=dev)
+    len_groups = torch.empty(N, int(g_out), dtype=torch.int32, device=dev)
+    source_group = torch.empty(N, int(g_out), dtype=torch.int32, device=dev)
+    rev = torch.empty(N, int(g_out), dtype=torch.bool, device=dev)
+    valid = torch.empty(N, dtype=torch.bool, device=dev)
+    _l.check(_l.load().dsvg_canonicalize(F32 if commands.dtype == torch.float32 else _l.DSVG_I64, commands.data_ptr(),
+                                         args.data_ptr(), N, G, S, int(g_out), int(s_out),
+                                         _l.DSVG_PATHS_CONCAT if concat else _l.DSVG_PATHS_GROUPED, int(numericalize),
+                                         out_c.data_ptr(), out_a.data_ptr(), n_groups.data_ptr(), len_groups.data_ptr(),
+                                         source_group.data_ptr(), rev.data_ptr(), valid.data_ptr(), _stream()),
+             "dsvg_canonicalize")
+    return {"commands": out_c, "args": out_a, "n_groups": n_groups, "len_groups": len_groups, "source_group": source_group,
+            "reversed": rev, "valid": valid}
+
+
+# ------------------------------------------------------------------------------------------------
 # device-side batch assembly (svgtensor_dataset.py:164-205)
 # ------------------------------------------------------------------------------------------------
 def assemble_batch(rows, slot_off, variant, G, L, grouped, want_args=True, want_rel=False, pad_val=-1.0,

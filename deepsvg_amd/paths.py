@@ -1,0 +1,99 @@
+"""The canonical form of a batch of icons, on the device: the way back into the model.  The encoder was trained on icons the
+reference preprocessed with ``SVG.canonicalize()`` followed by ``numericalize(256)`` (deepsvg/svglib/svg.py:333-349, 392-394):
+one sub-path per group, degenerate commands dropped, closed paths started at their top-left-most command, groups sorted top
+to bottom then left to right, clockwise orientation, no `z`, integer coordinates.  What `metrics.refine` /
+`render.refine_to_images` hand back (float arguments that have drifted), what ``greedy_sample`` decodes (any order and
+orientation, several `m` in a group, stray `z`) and what a user assembles by hand (notebooks/animation.ipynb: ``permute`` and
+``reverse`` by hand) are generally not in that form.  The reference canonicalises on the host, one icon at a time through Python
+objects; `canonicalize` is one launch of csrc/paths.hip for the whole batch.  Every output value is a copy of an input value
+- only the decisions are computed - so tests/golden/paths/ compares with the reference's own results by equality.
+
+The definition (include/dsvg.h; tests/paths_ref.py restates it in float64):
+ 1. rows: a group ends at its first EOS; the start point of a command is the end position (args 9:11) of the row before it;
+    rows before the group's first `m` are ignored; an `m` opens a sub-path and ends the one before it; a `z` marks the open
+    sub-path closed and ends it, rows after it are ignored until the next `m`.  Every sub-path becomes a group of its own, in
+    reading order.
+ 2. an `l` / `c` whose start and end are close (|s - e| <= 1e-8 + 1e-5 |e| in both coordinates) is dropped - a Bezier loop
+    that returns to its start too; a sub-path left without commands disappears.
+ 3. closed sub-paths are rotated to start at their top-left-most command: a running best over the commands in order, command
+    i (start p) replacing the best (start q) when p.y == q.y ? p.x < q.x : (p.y < q.y or (the fp32 norms of p and q are close
+    and p.x < q.x)).  As in the reference NO closing line is inserted: a closed sub-path whose last end is not its first start
+    keeps its rows, and the gap the `z` drew is lost.
+ 4. sub-paths are sorted by (start.y, start.x) of their first command, stable in reading order - BEFORE step 5, so the result
+    is generally not sorted by its final start points (the data sets were built this way).
+ 5. a sub-path of one command is clockwise when (start.x, start.y) <= (end.x, end.y), any other when the sum of start.x end.y
+    - start.y end.x over its commands is >= 0; one that is not is reversed (commands in reverse order, start and end swapped,
+    the control points of a `c` swapped).
+ 6. rows out: `m` with the first command's start, `l` with its end, `c` with control1, control2, end; never a `z`.
+ 7. numericalize=n: every enabled slot of the written rows becomes clip(round_half_even(v), 0, n - 1) after all decisions, which
+    are taken on the raw values; nothing is filtered again after rounding (the reference's data path does not either).  This is
+    ``Point.numericalize`` (svglib/geom.py:182-183) without the view-box rescale of ``SVG.numericalize``: arguments are taken
+    to be in the 0..256 box already, as everywhere in this package.
+The op is not idempotent in general (steps 4 and 5).  Arcs are out of scope, as in `metrics.sample_points` and the rasteriser.
+"""
+import torch
+
+from . import ops
+from .svgtensor import CMD_ARGS_MASK, C_ID
+
+__all__ = ["canonicalize", "numericalize"]
+
+MAX_ROWS = 2048      # G * S rows per icon: the largest icon the model accepts in a two-stage config, 8 groups of 256
+
+
+def canonicalize(commands, args, max_num_groups=None, max_seq_len=None, layout="grouped", numericalize=None):
+    """commands (N, G, S) with args (N, G, S, 11), or (N, S) with (N, S, 11) - read as G = 1, the one-stage layout with several
+    `m` in a sequence.  float32 (dataset, `refine`) and int64 (``greedy_sample``) are read as they are, anything else as
+    float32 (int64 arguments are compared as float32: exact below 2^24).  Inputs are detached; there is no gradient (the op is
+    piecewise constant in its decisions).  -> a dict, in the dtype read:
+      layout="grouped": "commands" (N, G_out, S_out), "args" (N, G_out, S_out, 11) as `dataset.batch` delivers commands_grouped /
+        args_grouped: a group in use is SOS, m, ..., EOS...; an unused one SOS, EOS...; every slot CMD_ARGS_MASK does not
+        enable is -1.  G_out = max_num_groups (default G; required for 2-D input), S_out = max_seq_len + 2 (default S).
+      layout="concat": "commands" (N, S_out), "args" (N, S_out, 11): SOS, all groups' rows back to back (each begins with its
+        `m`), EOS...: the dataset's `commands` / `args`.  max_seq_len is the total length here; max_num_groups still bounds
+        the number of sub-paths.
+      "n_groups" int32 [N]; "len_groups" int32 [N, G_out]: rows of each output group, its `m` included, 0 where unused;
+      "source_group" int32 [N, G_out]: the input group an output group came from, -1 where unused (per-group side data such as
+        `filling` follows with one gather); "reversed" bool [N, G_out]; "valid" bool [N].
+    An icon is invalid when it has more surviving sub-paths than G_out, when a sub-path (concat: all of them together) does not
+    fit S_out - 2 rows, or when it holds an `a` before its group's first EOS; it comes back as all-unused groups with n_groups
+    = 0 (as ``filter_meta`` drops such icons).  A closed sub-path whose last end is not its first start keeps its rows: the
+    reference inserts no closing line, and the gap is lost (module docstring, step 3)."""
+    if commands.dim() not in (2, 3) or args.dim() != commands.dim() + 1 or args.shape[:-1] != commands.shape \
+            or args.shape[-1] != 11:
+        raise ValueError(f"canonicalize: commands (N, G, S) with args (N, G, S, 11), or (N, S) with (N, S, 11); got "
+                         f"{tuple(commands.shape)} and {tuple(args.shape)}")
+    if layout not in ("grouped", "concat"):
+        raise ValueError(f"canonicalize: layout 'grouped' or 'concat'; got {layout!r}")
+    if commands.dim() == 2:
+        if max_num_groups is None:
+            raise ValueError("canonicalize: max_num_groups is required for (N, S) input")
+        commands, args = commands.unsqueeze(1), args.unsqueeze(1)
+    N, G, S = commands.shape
+    if N < 1:
+        raise ValueError("canonicalize: an empty batch")
+    if G * S > MAX_ROWS:
+        raise ValueError(f"canonicalize: {G} x {S} = {G * S} rows per icon, at most {MAX_ROWS}")
+    g_out = G if max_num_groups is None else int(max_num_groups)
+    s_out = S if max_seq_len is None else int(max_seq_len) + 2
+    if g_out < 1 or s_out < 2:
+        raise ValueError(f"canonicalize: max_num_groups >= 1 and max_seq_len >= 0; got {max_num_groups} and {max_seq_len}")
+    if numericalize is not None and int(numericalize) < 1:
+        raise ValueError(f"canonicalize: numericalize >= 1 or None; got {numericalize}")
+    commands, args = commands.detach(), args.detach()
+    if commands.dtype != args.dtype or commands.dtype not in (torch.float32, torch.int64):
+        commands, args = commands.float(), args.float()
+    return ops.canonicalize(commands.contiguous(), args.contiguous(), g_out, s_out, concat=layout == "concat",
+                            numericalize=0 if numericalize is None else int(numericalize))
+
+
+def numericalize(args, commands, n=256):
+    """step 7 on its own, elementwise: the slots CMD_ARGS_MASK enables for the row's command become clip(round_half_even(v), 0,
+    n - 1) (integer dtypes: clip only); every other slot is returned as it is.  Shapes (..., 11) and (...); same dtype out."""
+    if args.shape[:-1] != commands.shape or args.shape[-1] != 11:
+        raise ValueError(f"numericalize: args (..., 11) with commands (...); got {tuple(args.shape)} and {tuple(commands.shape)}")
+    args = args.detach()
+    cmd = commands.detach().long().clamp(0, CMD_ARGS_MASK.shape[0] - 1)
+    mask = CMD_ARGS_MASK.to(args.device)[cmd].bool() & (cmd <= C_ID).unsqueeze(-1)
+    rounded = args.clamp(0, n - 1) if not args.is_floating_point() else args.round().clamp(0, n - 1)
+    return torch.where(mask, rounded, args)

@@ -27,7 +27,7 @@ extern "C" {
 
 #define DSVG_F32 0
 #define DSVG_BF16 1
-#define DSVG_I64 2 /* an input dtype of dsvg_sample_points only */
+#define DSVG_I64 2 /* an input dtype of dsvg_sample_points / dsvg_raster_segments / dsvg_canonicalize only */
 
 /* ABI version: bumped on EVERY change of an exported signature (round 4: 2 - dsvg_ffn_bwd_one and
  * dsvg_attn_block_fwd_stages removed, round 3's signature changes of dsvg_defer_scope / dsvg_gather_groups /
@@ -52,8 +52,9 @@ extern "C" {
  * 17: dsvg_raster_sweep_nn / dsvg_raster_sweep_bwd / dsvg_raster_segments_bwd added (the gradient of an image).
  * 18: the one-launch attention input gradient of version 7 removed: its entry point, its workspace query and its debug clock
  *     (opt-in since round 6, never ahead of the two launches it replaced); a layer of dsvg_attn_pack_bwd is back to 128
- *     fragments (out_proj.weight^T only). */
-#define DSVG_ABI_VERSION 18
+ *     fragments (out_proj.weight^T only).
+ * 19: dsvg_canonicalize added (the canonical path order of SVG.canonicalize for a whole batch). */
+#define DSVG_ABI_VERSION 19
 
 const char* dsvg_last_error(void);
 int dsvg_version(void);
@@ -660,6 +661,52 @@ int dsvg_raster_sweep_bwd(const void* segs, const int32_t* seg_counts, const flo
                           int64_t B, int64_t cap, int32_t size, float stroke_width, int32_t flags, float* dsegs, void* stream);
 int dsvg_raster_segments_bwd(const float* commands, const float* dsegs, const int32_t* seg_counts, int64_t B, int32_t G,
                              int32_t L, int32_t n, int32_t fill, float* dargs, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Canonical path order of a batch (csrc/paths.hip): SVG.canonicalize() (deepsvg/svglib/svg.py:333-349) applied to
+ * SVG.from_tensors([group tensors]) and read back through to_tensor(concat_groups=False) (svg.py:141-166), optionally followed
+ * by Point.numericalize (svglib/geom.py:182-183) - the form the encoder was trained on.  Replaces the host loop over icons of
+ * the reference's preprocessing and of notebooks/animation.ipynb's permute / reverse by hand.  Every output value is a copy
+ * of an input value; only the decisions are computed.  The definition (tests/paths_ref.py restates it in float64; arcs are out
+ * of scope):
+ *  rows: commands [N, G, S] / args [N, G, S, 11] of dtype `itype` (DSVG_F32 or DSVG_I64; the decisions read DSVG_I64
+ *    coordinates as fp32, exact below 2^24, the values written are the int64 inputs), G * S <= 2048.  A group ends at its
+ *    first EOS; the start point of a row is the end position (args 9:11) of the row before it; rows before the group's first
+ *    `m` are ignored; an `m` opens a sub-path and ends the one before it; a `z` marks the open sub-path closed and ends it, and
+ *    rows after it are ignored until the next `m`.  Every sub-path becomes a group of its own, in reading order
+ *    (svglib/svg_path.py:118-157, split_paths).
+ *  degenerate commands (filter_consecutives, svg_path.py:214-220): an `l` / `c` with |s - e| <= 1e-8 + 1e-5 |e| in both
+ *    coordinates (float64) is dropped; a sub-path left without commands disappears.
+ *  rotation (reorder, svg_path.py:295-315), closed sub-paths only: a running best over the commands in order; command i with
+ *    start p replaces the best with start q when p.y == q.y ? p.x < q.x : (p.y < q.y || (the norms of p and q are close &&
+ *    p.x < q.x)) (svg_command.py:170-176).  The norm is the fp32 sqrt(x * x + y * y) (products, sum and square root each rounded
+ *    to fp32), the difference of the two norms is taken in fp32 and compared with 1e-8 + 1e-5 |norm q| in float64.  The
+ *    commands are rotated to start at the best.  No closing line is inserted: a closed sub-path whose last end is not its
+ *    first start loses the gap, as in the reference.
+ *  order (svg.py:343): sub-paths are sorted by (start.y, start.x) of their first command, stable in reading order - BEFORE
+ *    the orientation step, so the result is generally not sorted by its final start points.
+ *  orientation (svg_path.py:244-273): a sub-path of one command is clockwise when (s.x, s.y) <= (e.x, e.y) lexicographically,
+ *    any other when the float64 sum of s.x e.y - s.y e.x over its commands, in their order, is >= 0.  One that is not is
+ *    reversed: commands in reverse order, start and end swapped, the control points of a `c` swapped.
+ *  rows out: `m` with the first command's start, `l` with its end, `c` with control1, control2, end; never a `z`.
+ *  numericalize = n > 0: every enabled slot of the written rows becomes clip(round-half-even(v), 0, n - 1) (DSVG_I64: clip),
+ *    after all decisions.
+ *  layout DSVG_PATHS_GROUPED: out_commands [N, G_out, S_out] / out_args [N, G_out, S_out, 11] of dtype `itype`; a group in use
+ *    is SOS, m, ..., EOS...; an unused one SOS, EOS...; every slot CMD_ARGS_MASK does not enable is -1.
+ *  layout DSVG_PATHS_CONCAT: out_commands [N, S_out] / out_args [N, S_out, 11]: SOS, all groups' rows back to back, EOS....
+ *  n_groups int32 [N]; len_groups int32 [N, G_out]: rows of each output group, its `m` included, 0 where unused; source_group
+ *    int32 [N, G_out]: the input group, -1 where unused; reversed uint8 [N, G_out]; valid uint8 [N]: 0 when the icon has more
+ *    sub-paths than G_out, when a sub-path (concat: all of them together) has more than S_out - 2 rows, or when an `a` stands
+ *    before its group's first EOS; such an icon is written as all-unused groups with n_groups = 0.
+ *  One workgroup per icon: ballot prefix scans classify the rows, one lane per sub-path walks its commands for the rotation and
+ *    the determinant sum, a stable rank sort orders the sub-paths, and every output row gathers the input rows it copies.  No
+ *    atomics, no workspace, no device-to-host read: bit-reproducible, capturable. */
+#define DSVG_PATHS_GROUPED 0
+#define DSVG_PATHS_CONCAT 1
+int dsvg_canonicalize(int32_t itype, const void* commands, const void* args, int64_t N, int32_t G, int32_t S, int32_t G_out,
+                      int32_t S_out, int32_t layout, int32_t numericalize, void* out_commands, void* out_args,
+                      int32_t* n_groups, int32_t* len_groups, int32_t* source_group, uint8_t* reversed, uint8_t* valid,
+                      void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The argument head fused with its consumers (csrc/head_fused.hip): args_fcn = Linear(256 -> n_args *
