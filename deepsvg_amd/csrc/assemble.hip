@@ -12,12 +12,11 @@
 // Pure integer / byte movement: HBM-bound, 24 B read + 48..92 B written per output token; one thread per token,
 // consecutive threads write consecutive tokens.
 #include "dsvg_common.h"
+#include "svg_seq.h"             // N_ARGS, the command ids
 #include "../../include/dsvg.h"
 
 namespace {
-constexpr int N_ARGS = 11;
-constexpr int ROW_W = 12;          // int16 per stored row
-constexpr int CMD_EOS = 4, CMD_SOS = 5, N_CMD = 7;
+constexpr int ROW_W = N_ARGS + 1;  // int16 per stored row
 
 // deepsvg/difflib/tensor.py:15-21, bit a of entry c = CMD_ARGS_MASK[c][a]
 __device__ __constant__ uint32_t kCmdArgsMask[N_CMD] = {0x600u, 0x600u, 0x7E0u, 0x61Fu, 0u, 0u, 0u};
@@ -89,15 +88,16 @@ __global__ void assemble_kernel(const int16_t* __restrict__ rows, long long n_ro
             while (j >= begin) {                                 // previous real command (normally row r-1)
                 const int16_t* pr = rows + j * ROW_W;
                 if (pr[0] < CMD_EOS) {
-                    px = (float)pr[10];
-                    py = (float)pr[11];
+                    px = (float)pr[1 + ARG_END];
+                    py = (float)pr[2 + ARG_END];
                     found = true;
                     break;
                 }
                 --j;
             }
             if (found) {
-                v[5] -= px; v[6] -= py; v[7] -= px; v[8] -= py; v[9] -= px; v[10] -= py;
+#pragma unroll
+                for (int q = ARG_CONTROL1; q < N_ARGS; q += 2) { v[q] -= px; v[q + 1] -= py; }
             }
         }
         const uint32_t m = (c >= 0 && c < N_CMD) ? kCmdArgsMask[c] : 0u;

@@ -12,7 +12,7 @@
 //                       address: a broadcast), running minimum of the SQUARED distance, one sqrt per point after the
 //                       sweep; a one-thread-per-icon finish launch adds the slices in a fixed order.  No distance matrix,
 //                       no atomics.
-//   dsvg_chamfer_nn     the same sweep in a second kernel that also keeps the arg-min index (strict <: the lowest index
+//   dsvg_chamfer_nn     the same sweep, instantiated a second time, that also keeps the arg-min index (strict <: the lowest index
 //                       wins a tie); same minima, same sums, same finish launch, so `out` has dsvg_chamfer's bits.
 //   dsvg_chamfer_bwd    the same decomposition: a thread keeps up to 4 points of its cloud and their direct terms
 //                       u(x_i, y_j*(i)) / n_x in registers; the other cloud streams through LDS as (c_j, i*(j)) with
@@ -22,13 +22,10 @@
 //                       a token gathers the weighted sums of its own samples' gradients (columns 5..10) and the start-point
 //                       share of the row after it (columns 9, 10), in float64, and writes all 11 columns of its row.
 #include "dsvg_common.h"
-#include "flag_scan.h"           // SP_THREADS, SP_MAX_TOK, block_flag_scan (shared with raster.hip)
+#include "svg_seq.h"             // vocabulary, block_flag_scan and its scans, chamfer_count, the curve and its transpose
 #include "../../include/dsvg.h"
 
 namespace {
-constexpr int SP_N_ARGS = 11;
-constexpr int SP_CMD_L = 1, SP_CMD_C = 2;
-
 template <typename T>
 __global__ __launch_bounds__(SP_THREADS) void sample_points_kernel(const T* __restrict__ commands, const T* __restrict__ args,
                                                                    int G, int L, int n, long long cap,
@@ -41,15 +38,11 @@ __global__ __launch_bounds__(SP_THREADS) void sample_points_kernel(const T* __re
     const int tid = threadIdx.x;
     const int T_ = G * L;
     const T* cmd = commands + b * T_;
-    const T* arg = args + b * T_ * SP_N_ARGS;
+    const T* arg = args + b * T_ * N_ARGS;
 
     // ---- pass 1: where every drawing command's points go -----------------------------------------------------------
-    block_flag_scan(T_, pre, wtot, [&](int t) {
-        if (t >= T_) return false;
-        const int c = (int)cmd[t];
-        return c == SP_CMD_L || c == SP_CMD_C;
-    });
-    block_flag_scan(G, full, wtot, [&](int g) { return g < G && pre[(g + 1) * L] > pre[g * L]; });
+    block_flag_scan<SP_MAX_TOK>(T_, pre, wtot, [&](int t) { return is_drawing(cmd, t, T_); });
+    block_flag_scan<SP_MAX_TOK>(G, full, wtot, [&](int g) { return sequence_draws(pre, g, G, L); });
     for (int t = tid; t < T_; t += SP_THREADS)
         if (pre[t + 1] > pre[t]) src[pre[t]] = t;
     __syncthreads();
@@ -64,25 +57,15 @@ __global__ __launch_bounds__(SP_THREADS) void sample_points_kernel(const T* __re
         const int g = t / L, i = t - g * L;
         const bool last = j + 1 == pre[(g + 1) * L];
         if (k == n - 1 && !last) continue;
-        const T* a = arg + (long long)t * SP_N_ARGS;
-        // start point: the end position of the row before, whatever that row holds; (0, 0) on row 0 (tensor.py:75-82)
-        const float p0x = i ? (float)a[9 - SP_N_ARGS] : 0.f, p0y = i ? (float)a[10 - SP_N_ARGS] : 0.f;
-        const float p3x = (float)a[9], p3y = (float)a[10];
+        const T* a = arg + (long long)t * N_ARGS;
+        const float2 p0 = start_point(a, i);
+        const float p3x = (float)a[ARG_END], p3y = (float)a[ARG_END + 1];
         const float z = (float)k / (float)(n - 1);
-        float x, y;
-        if ((int)cmd[t] == SP_CMD_L) {
-            x = fmaf(z, p3x - p0x, p0x);
-            y = fmaf(z, p3y - p0y, p0y);
-        } else {
-            const float p1x = (float)a[5], p1y = (float)a[6], p2x = (float)a[7], p2y = (float)a[8];
-            // power basis of the cubic Bezier (exact for integer arguments), Horner in z
-            const float c1x = 3.f * (p1x - p0x), c2x = 3.f * (p0x - 2.f * p1x + p2x), c3x = (p3x - p0x) + 3.f * (p1x - p2x);
-            const float c1y = 3.f * (p1y - p0y), c2y = 3.f * (p0y - 2.f * p1y + p2y), c3y = (p3y - p0y) + 3.f * (p1y - p2y);
-            x = fmaf(fmaf(fmaf(c3x, z, c2x), z, c1x), z, p0x);
-            y = fmaf(fmaf(fmaf(c3y, z, c2y), z, c1y), z, p0y);
-        }
+        float2 v;
+        if ((int)cmd[t] == CMD_L) v = make_float2(fmaf(z, p3x - p0.x, p0.x), fmaf(z, p3y - p0.y, p0.y));
+        else v = CubicPower(p0, a, p3x, p3y).eval(p0, z);
         const long long o = (long long)pre[t] * (n - 1) + full[g] + k;
-        reinterpret_cast<float2*>(out)[o] = make_float2(x, y);
+        reinterpret_cast<float2*>(out)[o] = v;
     }
 }
 
@@ -102,54 +85,36 @@ __global__ __launch_bounds__(SP_THREADS) void sample_points_bwd_kernel(const flo
     const int tid = threadIdx.x;
     const int T_ = G * L;
     const float* cmd = commands + b * T_;
-    block_flag_scan(T_, pre, wtot, [&](int t) {
-        if (t >= T_) return false;
-        const int c = (int)cmd[t];
-        return c == SP_CMD_L || c == SP_CMD_C;
-    });
-    block_flag_scan(G, full, wtot, [&](int g) { return g < G && pre[(g + 1) * L] > pre[g * L]; });
+    block_flag_scan<SP_MAX_TOK>(T_, pre, wtot, [&](int t) { return is_drawing(cmd, t, T_); });
+    block_flag_scan<SP_MAX_TOK>(G, full, wtot, [&](int g) { return sequence_draws(pre, g, G, L); });
     const float2* dp = reinterpret_cast<const float2*>(dpoints) + b * cap;
-    float* out = dargs + b * T_ * SP_N_ARGS;
+    float* out = dargs + b * T_ * N_ARGS;
     const double step = 1.0 / (double)(n - 1);
     for (int t = tid; t < T_; t += SP_THREADS) {
         const int g = t / L, i = t - g * L;
         const int n_draw = pre[(g + 1) * L];              // drawing commands up to the end of this sequence
-        double c1x = 0.0, c1y = 0.0, c2x = 0.0, c2y = 0.0, ex = 0.0, ey = 0.0;
+        ArgRowGrad acc;
         const int c = (int)cmd[t];
-        if (c == SP_CMD_L || c == SP_CMD_C) {
+        if (c == CMD_L || c == CMD_C) {
             const long long o = (long long)pre[t] * (n - 1) + full[g];
             const int cnt = pre[t] + 1 == n_draw ? n : n - 1;
             for (int k = 0; k < cnt; ++k) {
                 const float2 d = dp[o + k];
-                const double z = (double)k * step, w = 1.0 - z;
-                if (c == SP_CMD_C) {
-                    const double w1 = 3.0 * w * w * z, w2 = 3.0 * w * z * z, w3 = z * z * z;
-                    c1x += w1 * (double)d.x; c1y += w1 * (double)d.y;
-                    c2x += w2 * (double)d.x; c2y += w2 * (double)d.y;
-                    ex += w3 * (double)d.x; ey += w3 * (double)d.y;
-                } else {
-                    ex += z * (double)d.x; ey += z * (double)d.y;
-                }
+                acc.own(c == CMD_C, (double)k * step, d.x, d.y);
             }
         }
         if (i + 1 < L) {
             const int c_next = (int)cmd[t + 1];
-            if (c_next == SP_CMD_L || c_next == SP_CMD_C) {
+            if (c_next == CMD_L || c_next == CMD_C) {
                 const long long o = (long long)pre[t + 1] * (n - 1) + full[g];
                 const int cnt = pre[t + 1] + 1 == n_draw ? n : n - 1;
                 for (int k = 0; k < cnt; ++k) {
                     const float2 d = dp[o + k];
-                    const double w = 1.0 - (double)k * step;
-                    const double w0 = c_next == SP_CMD_C ? w * w * w : w;
-                    ex += w0 * (double)d.x; ey += w0 * (double)d.y;
+                    acc.next_start(c_next == CMD_C, (double)k * step, (double)d.x, (double)d.y);
                 }
             }
         }
-        float* row = out + (long long)t * SP_N_ARGS;
-#pragma unroll
-        for (int q = 0; q < 5; ++q) row[q] = 0.f;
-        row[5] = (float)c1x; row[6] = (float)c1y; row[7] = (float)c2x; row[8] = (float)c2y;
-        row[9] = (float)ex; row[10] = (float)ey;
+        acc.store(out + (long long)t * N_ARGS);
     }
 }
 
@@ -160,29 +125,33 @@ constexpr int CH_R = 4;                   // chunks of 64 points a wave keeps in
 constexpr int CH_SLICE = CH_WAVES * CH_R * 64;      // points of one cloud per workgroup: 1,024
 constexpr int CH_TILE = 1024;             // points of the other cloud per LDS tile (8 KiB)
 
-// running minimum of the squared distance from R register points to the first cnt4 (a multiple of 4) points of the tile
-template <int R>
-__device__ __forceinline__ void chamfer_sweep(const float4* __restrict__ tile, int cnt4, const float2 (&x)[CH_R],
-                                              float (&m)[CH_R]) {
+// running minimum of the squared distance from R register points to the first cnt4 (a multiple of 4) points of the tile.
+// NN: a[r] = the index (j0 + position in the tile) of the first point that reached m[r]; the copies of the last point that
+// pad a tile can never win: strict <.  (`a` and j0 are not touched without NN.)
+template <bool NN, int R>
+__device__ __forceinline__ void chamfer_sweep(const float4* __restrict__ tile, int cnt4, int j0, const float2 (&x)[CH_R],
+                                              float (&m)[CH_R], int (&a)[CH_R]) {
 #pragma unroll 2
     for (int jj = 0; jj < cnt4 / 2; jj += 2) {
         const float4 q0 = tile[jj], q1 = tile[jj + 1];        // 4 points, the same address in every lane
+        const int j = j0 + 2 * jj;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
+            // (written out four times: a loop or a lambda over the four points schedules the arg-min kernel differently)
             float dx = x[r].x - q0.x, dy = x[r].y - q0.y;
-            m[r] = fminf(m[r], fmaf(dx, dx, dy * dy));
+            float d = fmaf(dx, dx, dy * dy);
+            if constexpr (NN) { if (d < m[r]) { m[r] = d; a[r] = j; } } else m[r] = fminf(m[r], d);
             dx = x[r].x - q0.z; dy = x[r].y - q0.w;
-            m[r] = fminf(m[r], fmaf(dx, dx, dy * dy));
+            d = fmaf(dx, dx, dy * dy);
+            if constexpr (NN) { if (d < m[r]) { m[r] = d; a[r] = j + 1; } } else m[r] = fminf(m[r], d);
             dx = x[r].x - q1.x; dy = x[r].y - q1.y;
-            m[r] = fminf(m[r], fmaf(dx, dx, dy * dy));
+            d = fmaf(dx, dx, dy * dy);
+            if constexpr (NN) { if (d < m[r]) { m[r] = d; a[r] = j + 2; } } else m[r] = fminf(m[r], d);
             dx = x[r].x - q1.z; dy = x[r].y - q1.w;
-            m[r] = fminf(m[r], fmaf(dx, dx, dy * dy));
+            d = fmaf(dx, dx, dy * dy);
+            if constexpr (NN) { if (d < m[r]) { m[r] = d; a[r] = j + 3; } } else m[r] = fminf(m[r], d);
         }
     }
-}
-
-__device__ __forceinline__ int chamfer_count(const int32_t* n, long long b, long long cap) {
-    return (int)min((long long)max(n[b], 0), cap);
 }
 
 // Workgroup (icon b, direction d, slice s): sum_i min_j |x_i - y_j| over the points i of slice s of cloud x (d = 0: x = px,
@@ -190,13 +159,16 @@ __device__ __forceinline__ int chamfer_count(const int32_t* n, long long b, long
 // numbers).  The 16 chunks of 64 points of a slice are dealt round-robin to the 4 waves, up to CH_R chunks per wave in
 // registers; y streams through the LDS tile.  part[(b * 2 + d) * n_slices + s] takes the sum; slices past the cloud's end
 // and icons with an empty cloud write nothing (the finish kernel does not read them).
-// chamfer_nn_slice_kernel below is this kernel plus the arg-min index and must write the same `part`: a change to the
-// chunk dealing, the tile padding, the distance expression or the order of the sums is made in both (a template parameter
-// would rename this kernel and move its registers; tests/test_metrics_grad_gpu.py compares the two outputs in bits).
+// NN: also idx_x[b, i] = arg-min_j |x_i - y_j| (d = 0) / idx_y[b, j] = arg-min_i |x_i - y_j| (d = 1) for the points in use
+// (idx_x / idx_y are not touched without NN); `part` takes the same numbers.  Both instantiations have, instruction for
+// instruction and in VGPRs, SGPRs, LDS and scratch, the code of the two separate kernels they replace
+// (profiles/geometry_header_isa.log); tests/test_metrics_grad_gpu.py compares the two outputs in bits.
+template <bool NN>
 __global__ __launch_bounds__(CH_THREADS) void chamfer_slice_kernel(const float* __restrict__ px, const int32_t* __restrict__ nx,
                                                                    long long capx, const float* __restrict__ py,
                                                                    const int32_t* __restrict__ ny, long long capy,
-                                                                   int n_slices, double* __restrict__ part) {
+                                                                   int n_slices, double* __restrict__ part,
+                                                                   int32_t* __restrict__ idx_x, int32_t* __restrict__ idx_y) {
     __shared__ __attribute__((aligned(16))) float2 tile[CH_TILE];
     __shared__ double red[CH_WAVES];
     const long long blk = blockIdx.x;
@@ -208,11 +180,13 @@ __global__ __launch_bounds__(CH_THREADS) void chamfer_slice_kernel(const float* 
     if (n_x == 0 || n_y == 0 || (long long)s * CH_SLICE >= n_x) return;      // (block-uniform)
     const float2* x = reinterpret_cast<const float2*>(swap ? py : px) + b * (swap ? capy : capx);
     const float2* y = reinterpret_cast<const float2*>(swap ? px : py) + b * (swap ? capx : capy);
+    int32_t* idx = (swap ? idx_y : idx_x) + b * (swap ? capy : capx);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n_chunks = (n_x + 63) >> 6;
 
     float2 xr[CH_R];
     float m[CH_R];
+    int am[CH_R];
     int nr = 0;                                        // chunks of this wave (wave-uniform)
 #pragma unroll
     for (int r = 0; r < CH_R; ++r) {
@@ -220,6 +194,7 @@ __global__ __launch_bounds__(CH_THREADS) void chamfer_slice_kernel(const float* 
         if (c < n_chunks) nr = r + 1;
         xr[r] = x[min(c * 64 + lane, n_x - 1)];
         m[r] = INFINITY;
+        am[r] = 0;
     }
     for (int j0 = 0; j0 < n_y; j0 += CH_TILE) {
         if (j0) __syncthreads();                       // the tile of the step before has been read
@@ -230,10 +205,10 @@ __global__ __launch_bounds__(CH_THREADS) void chamfer_slice_kernel(const float* 
         const int cnt4 = (min(CH_TILE, n_y - j0) + 3) & ~3;
         const float4* t4 = reinterpret_cast<const float4*>(tile);
         switch (nr) {
-            case 4: chamfer_sweep<4>(t4, cnt4, xr, m); break;
-            case 3: chamfer_sweep<3>(t4, cnt4, xr, m); break;
-            case 2: chamfer_sweep<2>(t4, cnt4, xr, m); break;
-            case 1: chamfer_sweep<1>(t4, cnt4, xr, m); break;
+            case 4: chamfer_sweep<NN, 4>(t4, cnt4, j0, xr, m, am); break;
+            case 3: chamfer_sweep<NN, 3>(t4, cnt4, j0, xr, m, am); break;
+            case 2: chamfer_sweep<NN, 2>(t4, cnt4, j0, xr, m, am); break;
+            case 1: chamfer_sweep<NN, 1>(t4, cnt4, j0, xr, m, am); break;
             default: break;
         }
     }
@@ -241,7 +216,10 @@ __global__ __launch_bounds__(CH_THREADS) void chamfer_slice_kernel(const float* 
 #pragma unroll
     for (int r = 0; r < CH_R; ++r) {
         const int c = s * (CH_SLICE / 64) + r * CH_WAVES + wave;
-        if (c < n_chunks && c * 64 + lane < n_x) sum += sqrtf(m[r]);
+        if (c < n_chunks && c * 64 + lane < n_x) {
+            sum += sqrtf(m[r]);
+            if constexpr (NN) idx[c * 64 + lane] = am[r];
+        }
     }
     // fixed-order sum: butterfly inside the wave, then the waves in ascending order
     double t = (double)sum;
@@ -277,105 +255,6 @@ __global__ __launch_bounds__(256) void chamfer_finish_kernel(const double* __res
         mean[d] = (float)(tot / (double)cnt[d]);
     }
     out[b] = mean[0] + mean[1];
-}
-
-// chamfer_sweep with the arg-min: a[r] = the index (j0 + position in the tile) of the first point that reached m[r].  The
-// copies of the last point that pad a tile can never win: strict <.
-template <int R>
-__device__ __forceinline__ void chamfer_sweep_nn(const float4* __restrict__ tile, int cnt4, int j0, const float2 (&x)[CH_R],
-                                                 float (&m)[CH_R], int (&a)[CH_R]) {
-#pragma unroll 2
-    for (int jj = 0; jj < cnt4 / 2; jj += 2) {
-        const float4 q0 = tile[jj], q1 = tile[jj + 1];
-        const int j = j0 + 2 * jj;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            float dx = x[r].x - q0.x, dy = x[r].y - q0.y;
-            float d = fmaf(dx, dx, dy * dy);
-            if (d < m[r]) { m[r] = d; a[r] = j; }
-            dx = x[r].x - q0.z; dy = x[r].y - q0.w;
-            d = fmaf(dx, dx, dy * dy);
-            if (d < m[r]) { m[r] = d; a[r] = j + 1; }
-            dx = x[r].x - q1.x; dy = x[r].y - q1.y;
-            d = fmaf(dx, dx, dy * dy);
-            if (d < m[r]) { m[r] = d; a[r] = j + 2; }
-            dx = x[r].x - q1.z; dy = x[r].y - q1.w;
-            d = fmaf(dx, dx, dy * dy);
-            if (d < m[r]) { m[r] = d; a[r] = j + 3; }
-        }
-    }
-}
-
-// chamfer_slice_kernel, and idx_x[b, i] = arg-min_j |x_i - y_j| (d = 0) / idx_y[b, j] = arg-min_i |x_i - y_j| (d = 1) for the
-// points in use.  A kernel of its own: the forward-only launch keeps its code.  The partial sums are the same numbers.
-__global__ __launch_bounds__(CH_THREADS) void chamfer_nn_slice_kernel(const float* __restrict__ px, const int32_t* __restrict__ nx,
-                                                                      long long capx, const float* __restrict__ py,
-                                                                      const int32_t* __restrict__ ny, long long capy,
-                                                                      int n_slices, double* __restrict__ part,
-                                                                      int32_t* __restrict__ idx_x, int32_t* __restrict__ idx_y) {
-    __shared__ __attribute__((aligned(16))) float2 tile[CH_TILE];
-    __shared__ double red[CH_WAVES];
-    const long long blk = blockIdx.x;
-    const int s = (int)(blk % n_slices);
-    const long long bd = blk / n_slices, b = bd >> 1;
-    const bool swap = bd & 1;
-    const int cx = chamfer_count(nx, b, capx), cy = chamfer_count(ny, b, capy);
-    const int n_x = swap ? cy : cx, n_y = swap ? cx : cy;
-    if (n_x == 0 || n_y == 0 || (long long)s * CH_SLICE >= n_x) return;      // (block-uniform)
-    const float2* x = reinterpret_cast<const float2*>(swap ? py : px) + b * (swap ? capy : capx);
-    const float2* y = reinterpret_cast<const float2*>(swap ? px : py) + b * (swap ? capx : capy);
-    int32_t* idx = (swap ? idx_y : idx_x) + b * (swap ? capy : capx);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n_chunks = (n_x + 63) >> 6;
-
-    float2 xr[CH_R];
-    float m[CH_R];
-    int am[CH_R];
-    int nr = 0;
-#pragma unroll
-    for (int r = 0; r < CH_R; ++r) {
-        const int c = s * (CH_SLICE / 64) + r * CH_WAVES + wave;
-        if (c < n_chunks) nr = r + 1;
-        xr[r] = x[min(c * 64 + lane, n_x - 1)];
-        m[r] = INFINITY;
-        am[r] = 0;
-    }
-    for (int j0 = 0; j0 < n_y; j0 += CH_TILE) {
-        if (j0) __syncthreads();
-#pragma unroll
-        for (int h = 0; h < CH_TILE / CH_THREADS; ++h)
-            tile[h * CH_THREADS + tid] = y[min(j0 + h * CH_THREADS + tid, n_y - 1)];
-        __syncthreads();
-        const int cnt4 = (min(CH_TILE, n_y - j0) + 3) & ~3;
-        const float4* t4 = reinterpret_cast<const float4*>(tile);
-        switch (nr) {
-            case 4: chamfer_sweep_nn<4>(t4, cnt4, j0, xr, m, am); break;
-            case 3: chamfer_sweep_nn<3>(t4, cnt4, j0, xr, m, am); break;
-            case 2: chamfer_sweep_nn<2>(t4, cnt4, j0, xr, m, am); break;
-            case 1: chamfer_sweep_nn<1>(t4, cnt4, j0, xr, m, am); break;
-            default: break;
-        }
-    }
-    float sum = 0.f;
-#pragma unroll
-    for (int r = 0; r < CH_R; ++r) {
-        const int c = s * (CH_SLICE / 64) + r * CH_WAVES + wave;
-        if (c < n_chunks && c * 64 + lane < n_x) {
-            sum += sqrtf(m[r]);
-            idx[c * 64 + lane] = am[r];
-        }
-    }
-    double t = (double)sum;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-    if (lane == 0) red[wave] = t;
-    __syncthreads();
-    if (tid == 0) {
-        double tot = 0.0;
-#pragma unroll
-        for (int w = 0; w < CH_WAVES; ++w) tot += red[w];
-        part[blk] = tot;
-    }
 }
 
 // (a - b) / (|a - b| cnt); 0 where a == b (and where a coordinate is NaN)
@@ -787,9 +666,7 @@ extern "C" int dsvg_sample_points(int32_t itype, const void* commands, const voi
                                   int32_t n, float* points, int32_t* counts, void* stream) {
     DSVG_CHECK_ARG(commands && args && points && counts, "sample_points: null pointer");
     DSVG_CHECK_ARG(itype == DSVG_F32 || itype == DSVG_I64, "sample_points: itype %d is neither DSVG_F32 nor DSVG_I64", itype);
-    DSVG_CHECK_ARG(n >= 2 && n <= 64, "sample_points: n = %d points per command, need 2..64", n);
-    DSVG_CHECK_ARG(B > 0 && B < (1ll << 31) && G >= 1 && L >= 1 && (int64_t)G * L <= SP_MAX_TOK,
-                   "sample_points: bad shape (B=%lld G=%d L=%d; G * L <= %d tokens per cloud)", (long long)B, G, L, SP_MAX_TOK);
+    if (sequence_args_ok("sample_points", "cloud", B, G, L, n)) return -1;
     const int64_t cap = (int64_t)G * ((int64_t)L * (n - 1) + 1);
     DSVG_CHECK_ARG(cap < (1ll << 31), "sample_points: %lld points per cloud do not fit int32", (long long)cap);
     hipStream_t st = (hipStream_t)stream;
@@ -808,62 +685,70 @@ extern "C" int64_t dsvg_chamfer_workspace_bytes(int64_t B, int64_t capx, int64_t
     return B * 2 * chamfer_slices(capx, capy) * (int64_t)sizeof(double);
 }
 
-extern "C" int dsvg_chamfer(const float* px, const int32_t* nx, int64_t capx, const float* py, const int32_t* ny,
-                            int64_t capy, int64_t B, float* out, void* workspace, int64_t workspace_bytes, void* stream) {
-    DSVG_CHECK_ARG(px && nx && py && ny && out && workspace, "chamfer: null pointer");
+namespace {
+// the arguments dsvg_chamfer, _nn and _bwd share, refused under the name of the caller; the workspace only `with_ws`.
+// -> *n_slices: slices per cloud and direction
+int chamfer_args_ok(const char* name, bool pointers, int64_t B, int64_t capx, int64_t capy, int64_t* n_slices, bool with_ws,
+                    const void* workspace, int64_t workspace_bytes) {
+    DSVG_CHECK_ARG(pointers, "%s: null pointer", name);
     DSVG_CHECK_ARG(B > 0 && B < (1ll << 31) && capx > 0 && capy > 0 && capx < (1ll << 31) && capy < (1ll << 31),
-                   "chamfer: bad shape (B=%lld capx=%lld capy=%lld; clouds hold 1 .. 2^31 - 1 points)", (long long)B,
+                   "%s: bad shape (B=%lld capx=%lld capy=%lld; clouds hold 1 .. 2^31 - 1 points)", name, (long long)B,
                    (long long)capx, (long long)capy);
-    const int64_t n_slices = chamfer_slices(capx, capy), blocks = B * 2 * n_slices;
-    DSVG_CHECK_ARG(blocks < (1ll << 31), "chamfer: %lld workgroups (B=%lld, %lld slices of %d points, 2 directions)",
-                   (long long)blocks, (long long)B, (long long)n_slices, CH_SLICE);
-    DSVG_CHECK_ARG(workspace_bytes >= dsvg_chamfer_workspace_bytes(B, capx, capy) && ((uintptr_t)workspace & 7) == 0,
-                   "chamfer: workspace of %lld bytes, need %lld (8-byte aligned)", (long long)workspace_bytes,
-                   (long long)dsvg_chamfer_workspace_bytes(B, capx, capy));
+    *n_slices = chamfer_slices(capx, capy);
+    const int64_t blocks = B * 2 * *n_slices;
+    DSVG_CHECK_ARG(blocks < (1ll << 31), "%s: %lld workgroups (B=%lld, %lld slices of %d points, 2 directions)", name,
+                   (long long)blocks, (long long)B, (long long)*n_slices, CH_SLICE);
+    if (with_ws)
+        DSVG_CHECK_ARG(workspace_bytes >= dsvg_chamfer_workspace_bytes(B, capx, capy) && ((uintptr_t)workspace & 7) == 0,
+                       "%s: workspace of %lld bytes, need %lld (8-byte aligned)", name, (long long)workspace_bytes,
+                       (long long)dsvg_chamfer_workspace_bytes(B, capx, capy));
+    return 0;
+}
+
+int chamfer_launch(const char* name, const float* px, const int32_t* nx, int64_t capx, const float* py, const int32_t* ny,
+                   int64_t capy, int64_t B, float* out, int32_t* idx_x, int32_t* idx_y, bool nn, void* workspace,
+                   int64_t workspace_bytes, void* stream) {
+    int64_t n_slices;
+    if (chamfer_args_ok(name, px && nx && py && ny && out && workspace && ((idx_x && idx_y) || !nn), B, capx, capy, &n_slices,
+                        true, workspace, workspace_bytes))
+        return -1;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(chamfer_slice_kernel, dim3((unsigned)blocks), dim3(CH_THREADS), 0, st, px, nx, (long long)capx, py, ny,
-                       (long long)capy, (int)n_slices, (double*)workspace);
-    DSVG_LAUNCH_CHECK("chamfer");
+    const dim3 grid((unsigned)(B * 2 * n_slices)), block(CH_THREADS);
+    if (nn)
+        hipLaunchKernelGGL(chamfer_slice_kernel<true>, grid, block, 0, st, px, nx, (long long)capx, py, ny, (long long)capy,
+                           (int)n_slices, (double*)workspace, idx_x, idx_y);
+    else
+        hipLaunchKernelGGL(chamfer_slice_kernel<false>, grid, block, 0, st, px, nx, (long long)capx, py, ny, (long long)capy,
+                           (int)n_slices, (double*)workspace, idx_x, idx_y);
+    DSVG_LAUNCH_CHECK(name);
     hipLaunchKernelGGL(chamfer_finish_kernel, dim3((unsigned)dsvg_cdiv(B, 256)), dim3(256), 0, st, (const double*)workspace,
                        nx, (long long)capx, ny, (long long)capy, (int)n_slices, (long long)B, out);
     DSVG_LAUNCH_CHECK("chamfer_finish");
     return 0;
+}
+}  // namespace
+
+extern "C" int dsvg_chamfer(const float* px, const int32_t* nx, int64_t capx, const float* py, const int32_t* ny,
+                            int64_t capy, int64_t B, float* out, void* workspace, int64_t workspace_bytes, void* stream) {
+    return chamfer_launch("chamfer", px, nx, capx, py, ny, capy, B, out, nullptr, nullptr, false, workspace, workspace_bytes,
+                          stream);
 }
 
 extern "C" int dsvg_chamfer_nn(const float* px, const int32_t* nx, int64_t capx, const float* py, const int32_t* ny,
                                int64_t capy, int64_t B, float* out, int32_t* idx_x, int32_t* idx_y, void* workspace,
                                int64_t workspace_bytes, void* stream) {
-    DSVG_CHECK_ARG(px && nx && py && ny && out && idx_x && idx_y && workspace, "chamfer_nn: null pointer");
-    DSVG_CHECK_ARG(B > 0 && B < (1ll << 31) && capx > 0 && capy > 0 && capx < (1ll << 31) && capy < (1ll << 31),
-                   "chamfer_nn: bad shape (B=%lld capx=%lld capy=%lld; clouds hold 1 .. 2^31 - 1 points)", (long long)B,
-                   (long long)capx, (long long)capy);
-    const int64_t n_slices = chamfer_slices(capx, capy), blocks = B * 2 * n_slices;
-    DSVG_CHECK_ARG(blocks < (1ll << 31), "chamfer_nn: %lld workgroups (B=%lld, %lld slices of %d points, 2 directions)",
-                   (long long)blocks, (long long)B, (long long)n_slices, CH_SLICE);
-    DSVG_CHECK_ARG(workspace_bytes >= dsvg_chamfer_workspace_bytes(B, capx, capy) && ((uintptr_t)workspace & 7) == 0,
-                   "chamfer_nn: workspace of %lld bytes, need %lld (8-byte aligned)", (long long)workspace_bytes,
-                   (long long)dsvg_chamfer_workspace_bytes(B, capx, capy));
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(chamfer_nn_slice_kernel, dim3((unsigned)blocks), dim3(CH_THREADS), 0, st, px, nx, (long long)capx, py,
-                       ny, (long long)capy, (int)n_slices, (double*)workspace, idx_x, idx_y);
-    DSVG_LAUNCH_CHECK("chamfer_nn");
-    hipLaunchKernelGGL(chamfer_finish_kernel, dim3((unsigned)dsvg_cdiv(B, 256)), dim3(256), 0, st, (const double*)workspace,
-                       nx, (long long)capx, ny, (long long)capy, (int)n_slices, (long long)B, out);
-    DSVG_LAUNCH_CHECK("chamfer_finish");
-    return 0;
+    return chamfer_launch("chamfer_nn", px, nx, capx, py, ny, capy, B, out, idx_x, idx_y, true, workspace, workspace_bytes,
+                          stream);
 }
 
 extern "C" int dsvg_chamfer_bwd(const float* px, const int32_t* nx, int64_t capx, const float* py, const int32_t* ny,
                                 int64_t capy, int64_t B, const int32_t* idx_x, const int32_t* idx_y, const float* dout,
                                 float* dpx, float* dpy, void* stream) {
-    DSVG_CHECK_ARG(px && nx && py && ny && idx_x && idx_y && dout && dpx && dpy, "chamfer_bwd: null pointer");
-    DSVG_CHECK_ARG(B > 0 && B < (1ll << 31) && capx > 0 && capy > 0 && capx < (1ll << 31) && capy < (1ll << 31),
-                   "chamfer_bwd: bad shape (B=%lld capx=%lld capy=%lld; clouds hold 1 .. 2^31 - 1 points)", (long long)B,
-                   (long long)capx, (long long)capy);
-    const int64_t n_slices = chamfer_slices(capx, capy), blocks = B * 2 * n_slices;
-    DSVG_CHECK_ARG(blocks < (1ll << 31), "chamfer_bwd: %lld workgroups (B=%lld, %lld slices of %d points, 2 directions)",
-                   (long long)blocks, (long long)B, (long long)n_slices, CH_SLICE);
-    hipLaunchKernelGGL(chamfer_bwd_kernel, dim3((unsigned)blocks), dim3(CH_THREADS), 0, (hipStream_t)stream, px, nx,
+    int64_t n_slices;
+    if (chamfer_args_ok("chamfer_bwd", px && nx && py && ny && idx_x && idx_y && dout && dpx && dpy, B, capx, capy, &n_slices,
+                        false, nullptr, 0))
+        return -1;
+    hipLaunchKernelGGL(chamfer_bwd_kernel, dim3((unsigned)(B * 2 * n_slices)), dim3(CH_THREADS), 0, (hipStream_t)stream, px, nx,
                        (long long)capx, py, ny, (long long)capy, idx_x, idx_y, dout, (int)n_slices, dpx, dpy);
     DSVG_LAUNCH_CHECK("chamfer_bwd");
     return 0;
@@ -872,10 +757,7 @@ extern "C" int dsvg_chamfer_bwd(const float* px, const int32_t* nx, int64_t capx
 extern "C" int dsvg_sample_points_bwd(const float* commands, int64_t B, int32_t G, int32_t L, int32_t n, const float* dpoints,
                                       float* dargs, void* stream) {
     DSVG_CHECK_ARG(commands && dpoints && dargs, "sample_points_bwd: null pointer");
-    DSVG_CHECK_ARG(n >= 2 && n <= 64, "sample_points_bwd: n = %d points per command, need 2..64", n);
-    DSVG_CHECK_ARG(B > 0 && B < (1ll << 31) && G >= 1 && L >= 1 && (int64_t)G * L <= SP_MAX_TOK,
-                   "sample_points_bwd: bad shape (B=%lld G=%d L=%d; G * L <= %d tokens per cloud)", (long long)B, G, L,
-                   SP_MAX_TOK);
+    if (sequence_args_ok("sample_points_bwd", "cloud", B, G, L, n)) return -1;
     const int64_t cap = (int64_t)G * ((int64_t)L * (n - 1) + 1);
     DSVG_CHECK_ARG(cap < (1ll << 31), "sample_points_bwd: %lld points per cloud do not fit int32", (long long)cap);
     hipLaunchKernelGGL(sample_points_bwd_kernel, dim3((unsigned)B), dim3(SP_THREADS), 0, (hipStream_t)stream, commands, G, L,

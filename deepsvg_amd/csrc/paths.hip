@@ -12,54 +12,18 @@
 // Every value written is a copy of an input value (or its rounded / clipped form with numericalize); no atomics, no workspace:
 // bit-reproducible, and nothing is read back to the host.
 #include "dsvg_common.h"
+#include "svg_seq.h"             // vocabulary, block_flag_scan (here with 16-bit counts: LDS is short)
 #include "../../include/dsvg.h"
 
 // the closeness tests and the determinant sum are restated operation by operation in tests/paths_ref.py: no fused multiply-add
 #pragma clang fp contract(off)
 
 namespace {
-constexpr int CP_THREADS = 256;
-constexpr int CP_MAX_ROWS = 2048;         // G * S rows of one icon: the largest two-stage config, 8 groups of 256
-constexpr int CP_N_ARGS = 11;
-constexpr int CP_M = 0, CP_L = 1, CP_C = 2, CP_A = 3, CP_EOS = 4, CP_SOS = 5, CP_Z = 6;
+constexpr int CP_THREADS = SP_THREADS;
+constexpr int CP_MAX_ROWS = SP_MAX_TOK;   // G * S rows of one icon: the largest two-stage config, 8 groups of 256
 constexpr int CP_DEAD = 255;              // class of a row at or behind its group's first EOS
 constexpr int CP_CLOSED = 1, CP_REVERSED = 2;
 typedef unsigned short cp_u16;
-
-// pre[t] = number of set flags among items < t, t in 0..n (pre[n] = the total); n >= 1.  flag(t) is called by every thread
-// for every t below the chunk-rounded n and must return false past n.  (flag_scan.h's scan with 16-bit counts.)
-template <int MAXT, typename F>
-__device__ __forceinline__ void cp_flag_scan(int n, cp_u16* __restrict__ pre, int* __restrict__ wtot, F flag) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n_chunks = (n + CP_THREADS - 1) / CP_THREADS;
-    int below[MAXT / CP_THREADS];
-#pragma unroll
-    for (int c = 0; c < MAXT / CP_THREADS; ++c) {
-        below[c] = 0;
-        if (c < n_chunks) {
-            const unsigned long long b = __ballot(flag(c * CP_THREADS + tid));
-            below[c] = __popcll(b & ((1ull << lane) - 1ull));
-            if (lane == 0) wtot[c * (CP_THREADS / 64) + wave] = __popcll(b);
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < MAXT / CP_THREADS; ++c) {
-        if (c < n_chunks) {
-            const int w = c * (CP_THREADS / 64) + wave;
-            int base = 0;
-            for (int q = 0; q < w; ++q) base += wtot[q];
-            const int t = c * CP_THREADS + tid;
-            if (t < n) pre[t] = (cp_u16)(base + below[c]);
-            if (t == n - 1) {
-                int tot = base;
-                for (int q = w; q < n_chunks * (CP_THREADS / 64); ++q) tot += wtot[q];
-                pre[n] = (cp_u16)tot;
-            }
-        }
-    }
-    __syncthreads();
-}
 
 // fp32 norm of Point.norm() (np.linalg.norm of a float32 pair): products, sum and root rounded to fp32 one by one.  The root
 // has to be the correctly rounded one: on the integer grid it alone decides the closeness test of two norms.  __fsqrt_rn is
@@ -103,38 +67,38 @@ __global__ __launch_bounds__(CP_THREADS) void canonicalize_kernel(
     const int tid = threadIdx.x;
     const int R = G * S;
     const T* cmd = commands + b * R;
-    const T* arg = args + b * R * CP_N_ARGS;
+    const T* arg = args + b * R * N_ARGS;
 
     // ---- rows in: class and end position -------------------------------------------------------------------------------
     for (int t = tid; t < R; t += CP_THREADS) {
         const int c = (int)cmd[t];
         cls[t] = (unsigned char)((c >= 0 && c <= 6) ? c : 7);
-        ex[t] = (float)arg[(long long)t * CP_N_ARGS + 9];
-        ey[t] = (float)arg[(long long)t * CP_N_ARGS + 10];
+        ex[t] = (float)arg[(long long)t * N_ARGS + ARG_END];
+        ey[t] = (float)arg[(long long)t * N_ARGS + ARG_END + 1];
     }
     if (tid == 0) s_bad = 0;
     __syncthreads();
 
     // ---- scan 1: a group ends at its first EOS -------------------------------------------------------------------------------
-    cp_flag_scan<MAXT>(R, pa, wtot, [&](int t) { return t < R && cls[t] == CP_EOS; });
+    block_flag_scan<MAXT>(R, pa, wtot, [&](int t) { return t < R && cls[t] == CMD_EOS; });
     for (int t = tid; t < R; t += CP_THREADS) {
         if (pa[t + 1] != pa[(t / S) * S]) cls[t] = CP_DEAD;
-        else if (cls[t] == CP_A) s_bad = 1;                                   // arcs are out of scope: the icon is invalid
+        else if (cls[t] == CMD_A) s_bad = 1;                                   // arcs are out of scope: the icon is invalid
     }
     __syncthreads();
 
     // ---- scan 2: markers; a row hangs on the last marker at or before it in its group -------------------------------
-    cp_flag_scan<MAXT>(R, pm, wtot, [&](int t) { return t < R && (cls[t] == CP_M || cls[t] == CP_Z); });
+    block_flag_scan<MAXT>(R, pm, wtot, [&](int t) { return t < R && (cls[t] == CMD_M || cls[t] == CMD_Z); });
     for (int t = tid; t < R; t += CP_THREADS)
         if (pm[t + 1] > pm[t]) markpos[pm[t]] = (cp_u16)t;
     __syncthreads();
     const int n_mark = pm[R];
 
     // ---- scan 3: the commands that stay: `l` / `c` under an `m`, not degenerate -------------------------------------
-    cp_flag_scan<MAXT>(R, pk, wtot, [&](int t) {
-        if (t >= R || (cls[t] != CP_L && cls[t] != CP_C)) return false;
+    block_flag_scan<MAXT>(R, pk, wtot, [&](int t) {
+        if (t >= R || (cls[t] != CMD_L && cls[t] != CMD_C)) return false;
         const int nm = pm[t + 1];
-        if (nm == pm[(t / S) * S] || cls[markpos[nm - 1]] != CP_M) return false;      // before the first m, or behind a z
+        if (nm == pm[(t / S) * S] || cls[markpos[nm - 1]] != CMD_M) return false;      // before the first m, or behind a z
         return !(cp_close(ex[t - 1], ex[t]) && cp_close(ey[t - 1], ey[t]));           // (t - 1 is in the group: the m is)
     });
     for (int t = tid; t < R; t += CP_THREADS)
@@ -146,10 +110,10 @@ __global__ __launch_bounds__(CP_THREADS) void canonicalize_kernel(
         const int g = markpos[k] / S;
         return (k + 1 < n_mark && markpos[k + 1] / S == g) ? (int)markpos[k + 1] : (g + 1) * S;
     };
-    cp_flag_scan<MAXT>(R, pa, wtot, [&](int k) {
+    block_flag_scan<MAXT>(R, pa, wtot, [&](int k) {
         if (k >= n_mark) return false;
         const int mr = markpos[k];
-        return cls[mr] == CP_M && pk[mark_end(k)] > pk[mr];
+        return cls[mr] == CMD_M && pk[mark_end(k)] > pk[mr];
     });
     const int P = pa[R];
     for (int k = tid; k < n_mark; k += CP_THREADS)
@@ -158,7 +122,7 @@ __global__ __launch_bounds__(CP_THREADS) void canonicalize_kernel(
             sp_j0[p] = pk[mr];
             sp_cnt[p] = (cp_u16)(pk[e] - pk[mr]);
             sp_grp[p] = (cp_u16)(mr / S);
-            sp_flag[p] = (e < (mr / S + 1) * S && cls[e] == CP_Z) ? CP_CLOSED : 0;
+            sp_flag[p] = (e < (mr / S + 1) * S && cls[e] == CMD_Z) ? CP_CLOSED : 0;
         }
     __syncthreads();
 
@@ -251,7 +215,7 @@ __global__ __launch_bounds__(CP_THREADS) void canonicalize_kernel(
     const int rows_out = layout == DSVG_PATHS_GROUPED ? G_out * S_out : S_out;
     const int n_used = ok ? P : 0;
     T* oc = out_cmd + b * rows_out;
-    T* oa = out_args + b * rows_out * CP_N_ARGS;
+    T* oa = out_args + b * rows_out * N_ARGS;
     for (int r = tid; r < rows_out; r += CP_THREADS) {
         int k = -1, i = 0;                    // output group and row inside it (0 = its m); k < 0: SOS / EOS
         int pos;
@@ -270,44 +234,45 @@ __global__ __launch_bounds__(CP_THREADS) void canonicalize_kernel(
                 k = lo; i = pos - 1 - off[lo];
             }
         }
-        T v[CP_N_ARGS];
+        T v[N_ARGS];
 #pragma unroll
-        for (int a = 0; a < CP_N_ARGS; ++a) v[a] = (T)-1;
-        int c_out = pos == 0 ? CP_SOS : CP_EOS;
+        for (int a = 0; a < N_ARGS; ++a) v[a] = (T)-1;
+        int c_out = pos == 0 ? CMD_SOS : CMD_EOS;
         if (k >= 0) {
             const int p = order[k];
             const int j0 = sp_j0[p], cnt = sp_cnt[p], best = sp_best[p];
             const bool rev = sp_flag[p] & CP_REVERSED;
-            int first = 9;                    // first enabled argument column
+            int first = ARG_END;              // first enabled argument column
             if (i == 0) {
-                c_out = CP_M;
+                c_out = CMD_M;
                 // the first command's start; reversed: the end of the command that was last
                 const int t = rev ? krow[j0 + (best + cnt - 1) % cnt] : krow[j0 + best] - 1;
-                v[9] = arg[(long long)t * CP_N_ARGS + 9];
-                v[10] = arg[(long long)t * CP_N_ARGS + 10];
+                v[ARG_END] = arg[(long long)t * N_ARGS + ARG_END];
+                v[ARG_END + 1] = arg[(long long)t * N_ARGS + ARG_END + 1];
             } else {
                 const int ci = rev ? cnt - i : i - 1;
                 const int t = krow[j0 + (best + ci) % cnt];
-                const T* a = arg + (long long)t * CP_N_ARGS;
+                const T* a = arg + (long long)t * N_ARGS;
                 c_out = cls[t];
-                const T* e = rev ? a - CP_N_ARGS : a;          // reversed: the command ends where it started
-                v[9] = e[9];
-                v[10] = e[10];
-                if (c_out == CP_C) {
-                    first = 5;
-                    v[5] = rev ? a[7] : a[5]; v[6] = rev ? a[8] : a[6];
-                    v[7] = rev ? a[5] : a[7]; v[8] = rev ? a[6] : a[8];
+                const T* e = rev ? a - N_ARGS : a;          // reversed: the command ends where it started
+                v[ARG_END] = e[ARG_END];
+                v[ARG_END + 1] = e[ARG_END + 1];
+                if (c_out == CMD_C) {
+                    first = ARG_CONTROL1;
+                    constexpr int C1 = ARG_CONTROL1, C2 = ARG_CONTROL2;
+                    v[C1] = rev ? a[C2] : a[C1]; v[C1 + 1] = rev ? a[C2 + 1] : a[C1 + 1];
+                    v[C2] = rev ? a[C1] : a[C2]; v[C2 + 1] = rev ? a[C1 + 1] : a[C2 + 1];
                 }
             }
             if (num > 0) {
 #pragma unroll
-                for (int a = 5; a < CP_N_ARGS; ++a)
+                for (int a = ARG_CONTROL1; a < N_ARGS; ++a)
                     if (a >= first) v[a] = cp_num(v[a], num);
             }
         }
         oc[r] = (T)c_out;
 #pragma unroll
-        for (int a = 0; a < CP_N_ARGS; ++a) oa[(long long)r * CP_N_ARGS + a] = v[a];
+        for (int a = 0; a < N_ARGS; ++a) oa[(long long)r * N_ARGS + a] = v[a];
     }
 }
 

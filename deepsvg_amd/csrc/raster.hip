@@ -23,12 +23,10 @@
 //                             scans, one thread per token gathers its own command's chords, the next row's (whose start point
 //                             is this row's end position) and the closing chords that start or end at it, in float64.
 #include "dsvg_common.h"
-#include "flag_scan.h"
+#include "svg_seq.h"
 #include "../../include/dsvg.h"
 
 namespace {
-constexpr int RS_N_ARGS = 11;
-constexpr int RS_CMD_L = 1, RS_CMD_C = 2;
 constexpr int RS_REC = 5;                 // words of a chord record: ax, ay, bx - ax, by - ay, flags
 constexpr int RS_THREADS = 256;
 constexpr int RS_TILE = 32;               // pixels per side of a workgroup's tile
@@ -58,19 +56,11 @@ __global__ __launch_bounds__(SP_THREADS) void raster_segments_kernel(const T* __
     const int tid = threadIdx.x;
     const int T_ = G * L;
     const T* cmd = commands + b * T_;
-    const T* arg = args + b * T_ * RS_N_ARGS;
+    const T* arg = args + b * T_ * N_ARGS;
 
     // ---- pass 1: where every command's chords and every sub-path's closing chord go --------------------------------------
-    block_flag_scan(T_, pre, wtot, [&](int t) {
-        if (t >= T_) return false;
-        const int c = (int)cmd[t];
-        return c == RS_CMD_L || c == RS_CMD_C;
-    });
-    // a sub-path ends at a drawing token that is the last row of its sequence or has a non-drawing row after it
-    block_flag_scan(T_, cl, wtot, [&](int t) {
-        if (!fill || t >= T_ || pre[t + 1] == pre[t]) return false;
-        return t % L == L - 1 || pre[t + 2] == pre[t + 1];
-    });
+    block_flag_scan<SP_MAX_TOK>(T_, pre, wtot, [&](int t) { return is_drawing(cmd, t, T_); });
+    block_flag_scan<SP_MAX_TOK>(T_, cl, wtot, [&](int t) { return subpath_ends(pre, t, T_, L, fill); });
     for (int t = tid; t < T_; t += SP_THREADS)
         if (pre[t + 1] > pre[t]) {
             src[pre[t]] = t;
@@ -85,10 +75,10 @@ __global__ __launch_bounds__(SP_THREADS) void raster_segments_kernel(const T* __
         float* r = out + o * RS_REC;
         r[0] = ax; r[1] = ay; r[2] = bx - ax; r[3] = by - ay; r[4] = __int_as_float(flags);
     };
-    // start point of token t: the end position of the row before, whatever that row holds; (0, 0) on row 0 (tensor.py:75-82)
+    // start point of token t, in the one-branch form (start_point's two selects load the coordinates one by one here)
     auto start_of = [&](int t) {
-        const T* a = arg + (long long)t * RS_N_ARGS;
-        return t % L ? make_float2((float)a[9 - RS_N_ARGS], (float)a[10 - RS_N_ARGS]) : make_float2(0.f, 0.f);
+        const T* a = arg + (long long)t * N_ARGS;
+        return t % L ? make_float2((float)a[ARG_END - N_ARGS], (float)a[ARG_END + 1 - N_ARGS]) : make_float2(0.f, 0.f);
     };
 
     // ---- pass 2: work item (j, k) = chord k (vertex k -> vertex k + 1) of the j-th drawing command ----------------------------
@@ -97,17 +87,12 @@ __global__ __launch_bounds__(SP_THREADS) void raster_segments_kernel(const T* __
         const int j = w / (n - 1), k = w - j * (n - 1);
         const int t = src[j];
         const int g = t / L;
-        const T* a = arg + (long long)t * RS_N_ARGS;
+        const T* a = arg + (long long)t * N_ARGS;
         const float2 p0 = start_of(t);
-        const float p3x = (float)a[9], p3y = (float)a[10];
-        const bool cubic = (int)cmd[t] == RS_CMD_C;
-        float c1x = 0.f, c1y = 0.f, c2x = 0.f, c2y = 0.f, c3x = 0.f, c3y = 0.f;
-        if (cubic) {
-            const float p1x = (float)a[5], p1y = (float)a[6], p2x = (float)a[7], p2y = (float)a[8];
-            // power basis of the cubic Bezier (exact for integer arguments), as sample_points_kernel
-            c1x = 3.f * (p1x - p0.x); c2x = 3.f * (p0.x - 2.f * p1x + p2x); c3x = (p3x - p0.x) + 3.f * (p1x - p2x);
-            c1y = 3.f * (p1y - p0.y); c2y = 3.f * (p0.y - 2.f * p1y + p2y); c3y = (p3y - p0.y) + 3.f * (p1y - p2y);
-        }
+        const float p3x = (float)a[ARG_END], p3y = (float)a[ARG_END + 1];
+        const bool cubic = (int)cmd[t] == CMD_C;
+        CubicPower curve;
+        if (cubic) curve = CubicPower(p0, a, p3x, p3y);
         // vertex q: the start point and the end position themselves at q = 0 and q = n - 1; between them Horner in z =
         // q / (n - 1) for `c`, and ((n - 1 - q) p0 + q p3) / (n - 1) for `l` (an exact numerator for integer arguments)
         float2 v[2];
@@ -117,10 +102,8 @@ __global__ __launch_bounds__(SP_THREADS) void raster_segments_kernel(const T* __
             const float fq = (float)q;
             if (q == 0) v[e] = p0;
             else if (q == n - 1) v[e] = make_float2(p3x, p3y);
-            else if (cubic) {
-                const float z = fq / nm1;
-                v[e] = make_float2(fmaf(fmaf(fmaf(c3x, z, c2x), z, c1x), z, p0.x), fmaf(fmaf(fmaf(c3y, z, c2y), z, c1y), z, p0.y));
-            } else {
+            else if (cubic) v[e] = curve.eval(p0, fq / nm1);
+            else {
                 const float fr = (float)(n - 1 - q);
                 v[e] = make_float2(fmaf(fq, p3x, fr * p0.x) / nm1, fmaf(fq, p3y, fr * p0.y) / nm1);
             }
@@ -132,9 +115,9 @@ __global__ __launch_bounds__(SP_THREADS) void raster_segments_kernel(const T* __
         for (int t = tid; t < T_; t += SP_THREADS)
             if (cl[t + 1] > cl[t]) {
                 const int tf = first[cl[t]];
-                const T* a = arg + (long long)t * RS_N_ARGS;
+                const T* a = arg + (long long)t * N_ARGS;
                 const float2 p = start_of(tf);
-                put((long long)(pre[t] + 1) * (n - 1) + cl[t], (float)a[9], (float)a[10], p.x, p.y,
+                put((long long)(pre[t] + 1) * (n - 1) + cl[t], (float)a[ARG_END], (float)a[ARG_END + 1], p.x, p.y,
                     ((pre[t] + 1 - pre[tf]) * (n - 1)) << 1);
             }
 }
@@ -157,7 +140,7 @@ __global__ __launch_bounds__(RS_THREADS) void raster_sweep_kernel(const float* _
     const long long blk = blockIdx.x;
     const int tx = (int)(blk % tiles), ty = (int)((blk / tiles) % tiles);
     const long long b = blk / ((long long)tiles * tiles);
-    const int cnt = (int)min((long long)max(seg_counts[b], 0), cap);
+    const int cnt = chamfer_count(seg_counts, b, cap);
     const float* sg = segs + b * cap * RS_REC;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int col0 = tx * RS_TILE + (wave & 1) * RS_QUAD, row0 = ty * RS_TILE + (wave >> 1) * RS_QUAD;
@@ -292,7 +275,7 @@ __global__ __launch_bounds__(RB_THREADS) void raster_sweep_bwd_kernel(const floa
     const long long b = blockIdx.x / blocks_per_image;
     const int j = (int)(blockIdx.x % blocks_per_image) * PER + (int)threadIdx.x / GW;
     const int l = (int)threadIdx.x % GW;
-    const int cnt = (int)min((long long)max(seg_counts[b], 0), cap);
+    const int cnt = chamfer_count(seg_counts, b, cap);
     if (j >= cnt) return;                                 // whole groups leave: the shuffles below stay inside a group
     const float* r = segs + (b * cap + j) * RS_REC;
     const float ax = r[0], ay = r[1], dx = r[2], dy = r[3];
@@ -353,29 +336,23 @@ __global__ __launch_bounds__(SP_THREADS) void raster_segments_bwd_kernel(const f
     const int tid = threadIdx.x;
     const int T_ = G * L;
     const float* cmd = commands + b * T_;
-    block_flag_scan(T_, pre, wtot, [&](int t) {
-        if (t >= T_) return false;
-        const int c = (int)cmd[t];
-        return c == RS_CMD_L || c == RS_CMD_C;
-    });
-    block_flag_scan(T_, cl, wtot, [&](int t) {
-        if (!fill || t >= T_ || pre[t + 1] == pre[t]) return false;
-        return t % L == L - 1 || pre[t + 2] == pre[t + 1];
-    });
+    block_flag_scan<SP_MAX_TOK>(T_, pre, wtot, [&](int t) { return is_drawing(cmd, t, T_); });
+    block_flag_scan<SP_MAX_TOK>(T_, cl, wtot, [&](int t) { return subpath_ends(pre, t, T_, L, fill); });
     for (int t = tid; t < T_; t += SP_THREADS)
         if (cl[t + 1] > cl[t]) last[cl[t]] = t;
     __syncthreads();
-    const int cnt = (int)min((long long)max(seg_counts[b], 0), cap);
+    const int cnt = chamfer_count(seg_counts, b, cap);
     const float4* ds = reinterpret_cast<const float4*>(dsegs) + b * cap;
     auto rec = [&](int o) { return o < cnt ? ds[o] : make_float4(0.f, 0.f, 0.f, 0.f); };
-    float* out = dargs + b * T_ * RS_N_ARGS;
+    float* out = dargs + b * T_ * N_ARGS;
     const double step = 1.0 / (double)(n - 1);
     for (int t = tid; t < T_; t += SP_THREADS) {
         const int i = t % L;
+        // (ArgRowGrad of svg_seq.h written out: with the struct, or its updates as functions, hipcc orders this kernel differently)
         double c1x = 0.0, c1y = 0.0, c2x = 0.0, c2y = 0.0, ex = 0.0, ey = 0.0;
         const bool draws = pre[t + 1] > pre[t];
         if (draws) {
-            const bool cubic = (int)cmd[t] == RS_CMD_C;
+            const bool cubic = (int)cmd[t] == CMD_C;
             const int o = pre[t] * (n - 1) + cl[t];
             for (int q = 1; q < n; ++q) {                  // (vertex 0 has no weight on this row)
                 const float4 lo = rec(o + q - 1);
@@ -397,7 +374,7 @@ __global__ __launch_bounds__(SP_THREADS) void raster_segments_bwd_kernel(const f
         }
         const bool next_draws = i + 1 < L && pre[t + 2] > pre[t + 1];
         if (next_draws) {
-            const bool cubic = (int)cmd[t + 1] == RS_CMD_C;
+            const bool cubic = (int)cmd[t + 1] == CMD_C;
             const int o = pre[t + 1] * (n - 1) + cl[t + 1];
             for (int q = 0; q < n - 1; ++q) {              // (vertex n - 1 has no weight on the start point)
                 const float4 hi = rec(o + q);
@@ -422,7 +399,7 @@ __global__ __launch_bounds__(SP_THREADS) void raster_segments_bwd_kernel(const f
                 ex += (double)c.z; ey += (double)c.w;
             }
         }
-        float* row = out + (long long)t * RS_N_ARGS;
+        float* row = out + (long long)t * N_ARGS;
 #pragma unroll
         for (int q = 0; q < 5; ++q) row[q] = 0.f;
         row[5] = (float)c1x; row[6] = (float)c1y; row[7] = (float)c2x; row[8] = (float)c2y;
@@ -440,9 +417,7 @@ extern "C" int dsvg_raster_segments(int32_t itype, const void* commands, const v
                                     int32_t n, int32_t fill, void* segs, int64_t segs_bytes, int32_t* seg_counts, void* stream) {
     DSVG_CHECK_ARG(commands && args && segs && seg_counts, "raster_segments: null pointer");
     DSVG_CHECK_ARG(itype == DSVG_F32 || itype == DSVG_I64, "raster_segments: itype %d is neither DSVG_F32 nor DSVG_I64", itype);
-    DSVG_CHECK_ARG(n >= 2 && n <= 64, "raster_segments: n = %d points per command, need 2..64", n);
-    DSVG_CHECK_ARG(B > 0 && B < (1ll << 31) && G >= 1 && L >= 1 && (int64_t)G * L <= SP_MAX_TOK,
-                   "raster_segments: bad shape (B=%lld G=%d L=%d; G * L <= %d tokens per image)", (long long)B, G, L, SP_MAX_TOK);
+    if (sequence_args_ok("raster_segments", "image", B, G, L, n)) return -1;
     const int64_t cap = raster_cap(G, L, n, fill);      // <= 2048 * 64: far below 2^31
     DSVG_CHECK_ARG(segs_bytes >= dsvg_raster_workspace_bytes(B, G, L, n, fill) && ((uintptr_t)segs & 3) == 0,
                    "raster_segments: buffer of %lld bytes, need %lld (4-byte aligned)", (long long)segs_bytes,
@@ -543,10 +518,7 @@ extern "C" int dsvg_raster_sweep_bwd(const void* segs, const int32_t* seg_counts
 extern "C" int dsvg_raster_segments_bwd(const float* commands, const float* dsegs, const int32_t* seg_counts, int64_t B,
                                         int32_t G, int32_t L, int32_t n, int32_t fill, float* dargs, void* stream) {
     DSVG_CHECK_ARG(commands && dsegs && seg_counts && dargs, "raster_segments_bwd: null pointer");
-    DSVG_CHECK_ARG(n >= 2 && n <= 64, "raster_segments_bwd: n = %d points per command, need 2..64", n);
-    DSVG_CHECK_ARG(B > 0 && B < (1ll << 31) && G >= 1 && L >= 1 && (int64_t)G * L <= SP_MAX_TOK,
-                   "raster_segments_bwd: bad shape (B=%lld G=%d L=%d; G * L <= %d tokens per image)", (long long)B, G, L,
-                   SP_MAX_TOK);
+    if (sequence_args_ok("raster_segments_bwd", "image", B, G, L, n)) return -1;
     DSVG_CHECK_ARG(((uintptr_t)dsegs & 15) == 0, "raster_segments_bwd: dsegs must be 16-byte aligned");
     hipLaunchKernelGGL(raster_segments_bwd_kernel, dim3((unsigned)B), dim3(SP_THREADS), 0, (hipStream_t)stream, commands, dsegs,
                        seg_counts, G, L, n, fill ? 1 : 0, (long long)raster_cap(G, L, n, fill), dargs);

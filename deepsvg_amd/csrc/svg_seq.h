@@ -1,0 +1,154 @@
+// Sequences of drawing commands on the device, stated once for csrc/metrics.hip (sample_points and its backward),
+// csrc/raster.hip (the chords of an image and their backward), csrc/paths.hip (canonical path order) and
+// csrc/assemble.hip (batch assembly): the command vocabulary and the argument columns of SVGTensor
+// (deepsvg/difflib/tensor.py:8-41), the ballot prefix scan that gives every drawing command its output offset and the
+// scans built on it, the count clamp of a cloud, and the curve a drawing command draws with its transpose.
+//
+// The contracts that live here: the rasteriser's vertices are sample_points' points, and the backward kernels run on the
+// forward's offsets.  A drawing command (`l`, `c`) of token t starts at the end position of the row before it, whatever that
+// row holds, and at (0, 0) on row 0 of its sequence (tensor.py:75-82).  A `c` is evaluated in the power basis of CubicPower,
+// Horner in z.  The straight line is NOT shared, on purpose: sample_points takes fma(z, p3 - p0, p0), the rasteriser the
+// exact numerator ((n - 1 - q) p0 + q p3) / (n - 1) with vertex 0 and vertex n - 1 the start point and the end position bit for
+// bit, so that consecutive chords share their vertices exactly; each kernel keeps its own.
+#pragma once
+#include "dsvg_common.h"
+
+namespace {
+// ---- vocabulary and layout -------------------------------------------------------------------------------------------
+constexpr int CMD_M = 0, CMD_L = 1, CMD_C = 2, CMD_A = 3, CMD_EOS = 4, CMD_SOS = 5, CMD_Z = 6, N_CMD = 7;
+constexpr int N_ARGS = 11;                // rx, ry, phi, fA, fS, control1 (x, y), control2 (x, y), end (x, y)
+constexpr int ARG_CONTROL1 = 5, ARG_CONTROL2 = 7, ARG_END = 9;      // column of x; y is the column after it
+
+constexpr int SP_THREADS = 256;
+constexpr int SP_MAX_TOK = 2048;          // G * L tokens of one cloud / image / icon: 8 chunks of 256
+
+// ---- the scan ----------------------------------------------------------------------------------------------------------
+// Exclusive prefix count of a flag by one workgroup of SP_THREADS threads: a ballot per wave and chunk, then a prefix sum
+// over the wave totals.  pre[t] = number of set flags among items < t, for t in 0..n (pre[n] = the total), 1 <= n <= MAXT (a
+// multiple of SP_THREADS: the chunks are unrolled into registers); C = int, or a 16-bit type where LDS is short.  flag(t) is
+// called by every thread for t < the chunk-rounded n and must return false past n.  wtot: one slot per wave of every chunk.
+template <int MAXT, typename C, typename F>
+__device__ __forceinline__ void block_flag_scan(int n, C* __restrict__ pre, int* __restrict__ wtot, F flag) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n_chunks = (n + SP_THREADS - 1) / SP_THREADS;
+    int below[MAXT / SP_THREADS];           // flags below this lane inside its wave, per chunk (unrolled: registers)
+#pragma unroll
+    for (int c = 0; c < MAXT / SP_THREADS; ++c) {
+        below[c] = 0;
+        if (c < n_chunks) {
+            const unsigned long long b = __ballot(flag(c * SP_THREADS + tid));
+            below[c] = __popcll(b & ((1ull << lane) - 1ull));
+            if (lane == 0) wtot[c * (SP_THREADS / 64) + wave] = __popcll(b);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < MAXT / SP_THREADS; ++c) {
+        if (c < n_chunks) {
+            const int w = c * (SP_THREADS / 64) + wave;
+            int base = 0;
+            for (int q = 0; q < w; ++q) base += wtot[q];      // <= 31 broadcast reads
+            const int t = c * SP_THREADS + tid;
+            if (t < n) pre[t] = (C)(base + below[c]);
+            if (t == n - 1) {
+                int tot = base;
+                for (int q = w; q < n_chunks * (SP_THREADS / 64); ++q) tot += wtot[q];
+                pre[n] = (C)tot;
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// The three flags the geometry kernels scan with block_flag_scan<SP_MAX_TOK> over int counts, forward and backward alike.
+// They are predicates called from a [&] lambda at the scan: a function that wraps the scan, or one that returns the lambda,
+// moves the registers of sample_points_kernel and sample_points_bwd_kernel.
+// pre[t] = drawing commands (`l`, `c`) among the tokens before t: token t of the T_ tokens at cmd draws
+template <typename T>
+__device__ __forceinline__ bool is_drawing(const T* cmd, int t, int T_) {
+    if (t >= T_) return false;
+    const int c = (int)cmd[t];
+    return c == CMD_L || c == CMD_C;
+}
+// full[g] = sequences with at least one drawing command among the sequences before g: sequence g of G has one
+__device__ __forceinline__ bool sequence_draws(const int* pre, int g, int G, int L) {
+    return g < G && pre[(g + 1) * L] > pre[g * L];
+}
+// cl[t] = sub-paths that end before token t (fill mode; all zero otherwise): a sub-path ends at a drawing token that is the
+// last row of its sequence or has a non-drawing row after it
+__device__ __forceinline__ bool subpath_ends(const int* pre, int t, const int& T_, const int& L, const int& fill) {
+    if (!fill || t >= T_ || pre[t + 1] == pre[t]) return false;
+    return t % L == L - 1 || pre[t + 2] == pre[t + 1];
+}
+
+// ---- the count clamp: the points (records) in use of cloud b, whatever n[b] holds ------------------------------------
+__device__ __forceinline__ int chamfer_count(const int32_t* n, long long b, long long cap) {
+    return (int)min((long long)max(n[b], 0), cap);
+}
+
+// ---- curve evaluation ----------------------------------------------------------------------------------------------------
+// start point of the token whose argument row is `a`, row i of its sequence
+template <typename T>
+__device__ __forceinline__ float2 start_point(const T* a, int i) {
+    return make_float2(i ? (float)a[ARG_END - N_ARGS] : 0.f, i ? (float)a[ARG_END + 1 - N_ARGS] : 0.f);
+}
+
+// power basis of the cubic Bezier p0..p3 (exact for integer arguments), Horner in z
+struct CubicPower {
+    float c1x = 0.f, c1y = 0.f, c2x = 0.f, c2y = 0.f, c3x = 0.f, c3y = 0.f;
+    CubicPower() = default;
+    template <typename T>
+    __device__ __forceinline__ CubicPower(float2 p0, const T* a, float p3x, float p3y) {
+        const float p1x = (float)a[ARG_CONTROL1], p1y = (float)a[ARG_CONTROL1 + 1];
+        const float p2x = (float)a[ARG_CONTROL2], p2y = (float)a[ARG_CONTROL2 + 1];
+        c1x = 3.f * (p1x - p0.x); c2x = 3.f * (p0.x - 2.f * p1x + p2x); c3x = (p3x - p0.x) + 3.f * (p1x - p2x);
+        c1y = 3.f * (p1y - p0.y); c2y = 3.f * (p0.y - 2.f * p1y + p2y); c3y = (p3y - p0.y) + 3.f * (p1y - p2y);
+    }
+    __device__ __forceinline__ float2 eval(float2 p0, float z) const {
+        return make_float2(fmaf(fmaf(fmaf(c3x, z, c2x), z, c1x), z, p0.x), fmaf(fmaf(fmaf(c3y, z, c2y), z, c1y), z, p0.y));
+    }
+};
+
+// The transpose: the gradient of one argument row, float64 sums of the gradients (vx, vy) of the curve's vertices times the
+// Bernstein weights CubicPower evaluates (`c`) or (1 - z, z) (`l`); the result is the float32 nearest to the exact sum.
+struct ArgRowGrad {
+    double c1x = 0.0, c1y = 0.0, c2x = 0.0, c2y = 0.0, ex = 0.0, ey = 0.0;
+    // the vertex at z of this row's own command: control1, control2, end.  (V: float or double, widened where it is used)
+    template <typename V>
+    __device__ __forceinline__ void own(bool cubic, double z, V vx, V vy) {
+        const double w = 1.0 - z;
+        if (cubic) {
+            const double w1 = 3.0 * w * w * z, w2 = 3.0 * w * z * z, w3 = z * z * z;
+            c1x += w1 * (double)vx; c1y += w1 * (double)vy;
+            c2x += w2 * (double)vx; c2y += w2 * (double)vy;
+            ex += w3 * (double)vx; ey += w3 * (double)vy;
+        } else {
+            ex += z * (double)vx; ey += z * (double)vy;
+        }
+    }
+    // the vertex at z of the command on the row after this one: its start point is this row's end position
+    template <typename V>
+    __device__ __forceinline__ void next_start(bool cubic, double z, V vx, V vy) {
+        const double w = 1.0 - z;
+        const double w0 = cubic ? w * w * w : w;
+        ex += w0 * (double)vx; ey += w0 * (double)vy;
+    }
+    // every element of the row is written
+    __device__ __forceinline__ void store(float* row) const {
+#pragma unroll
+        for (int q = 0; q < ARG_CONTROL1; ++q) row[q] = 0.f;
+        row[ARG_CONTROL1] = (float)c1x; row[ARG_CONTROL1 + 1] = (float)c1y;
+        row[ARG_CONTROL2] = (float)c2x; row[ARG_CONTROL2 + 1] = (float)c2y;
+        row[ARG_END] = (float)ex; row[ARG_END + 1] = (float)ey;
+    }
+};
+
+// ---- host: the (B, G, L, n) arguments dsvg_sample_points, dsvg_raster_segments and their backwards share, refused under the
+// name of the caller; `noun` is what a workgroup builds from its G * L tokens ("cloud", "image")
+inline int sequence_args_ok(const char* name, const char* noun, int64_t B, int32_t G, int32_t L, int32_t n) {
+    DSVG_CHECK_ARG(n >= 2 && n <= 64, "%s: n = %d points per command, need 2..64", name, n);
+    DSVG_CHECK_ARG(B > 0 && B < (1ll << 31) && G >= 1 && L >= 1 && (int64_t)G * L <= SP_MAX_TOK,
+                   "%s: bad shape (B=%lld G=%d L=%d; G * L <= %d tokens per %s)", name, (long long)B, G, L, SP_MAX_TOK, noun);
+    return 0;
+}
+}  // namespace

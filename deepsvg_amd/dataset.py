@@ -30,12 +30,12 @@ import torch.utils.data
 
 from . import ops
 from .lib import DsvgError
+from .svgtensor import N_ARGS
 
 # columns of a stored 14-wide row that SVGTensor.from_data keeps (deepsvg/difflib/tensor.py:23-32,85-88): the command
 # and the 11 arg_keys columns (radius, x_axis_rot, large_arc_flg, sweep_flg, control1, control2, end_pos); START_POS
 # (6:8) is derived data the tensors never read
 ROW_COLS = (0, 1, 2, 3, 4, 5, 8, 9, 10, 11, 12, 13)
-N_ARGS = 11
 
 # svgtensor_dataset.py:77-85
 _CATEGORIES = ['characters', 'free-icons', 'logos', 'alphabet', 'animals', 'arrows', 'astrology', 'baby', 'beauty',

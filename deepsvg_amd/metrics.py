@@ -21,6 +21,8 @@ shift are properties of the input (the lowest index wins every tie); the gradien
 the target is a constant, as in the notebook.  `polyline_length`, `svg_length_loss` (:15-18) and `continuity_loss` (:10-12)
 complete the file; `emd_loss` is the batch loss and ``refine(loss="emd")`` the notebook's loop with the notebook's loss.
 """
+import contextlib
+
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -95,6 +97,51 @@ class _PolylineLength(torch.autograd.Function):
         return ops.polyline_length_bwd(*ctx.saved_tensors, dout.contiguous()), None
 
 
+def _flat_sequences(name, commands, args):
+    """commands (N, S) or (N, G, S) with args (..., S, 11), refused under the caller's `name` -> (commands [N * G, S], args
+    [N * G, S, 11], G): contiguous, and both float32 unless they are both float32 or both int64 already"""
+    if commands.dim() not in (2, 3) or args.dim() != commands.dim() + 1 or args.shape[:-1] != commands.shape:
+        raise ValueError(f"{name}: commands (N, S) or (N, G, S) with args (..., S, 11); got {tuple(commands.shape)} "
+                         f"and {tuple(args.shape)}")
+    if commands.dtype != args.dtype or commands.dtype not in (torch.float32, torch.int64):
+        commands, args = commands.float(), args.float()
+    groups = commands.shape[1] if commands.dim() == 3 else 1
+    S = commands.shape[-1]
+    return commands.reshape(-1, S).contiguous(), args.reshape(-1, S, args.shape[-1]).contiguous(), groups
+
+
+@contextlib.contextmanager
+def _evaluating(model):
+    """eval mode and no gradients inside; the model's train / eval state is restored"""
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            yield
+    finally:
+        model.train(was_training)
+
+
+def _masked_mean(per_icon, valid):
+    """the mean of `per_icon` over the `valid` icons: the others are masked out before the sum; NaN when there is none"""
+    return torch.where(valid, per_icon, torch.zeros_like(per_icon)).sum() / valid.sum()
+
+
+def _adam_refine(args, steps, lr, batch_loss):
+    """Adam on a float32 copy of `args`, minimising the 0-d batch_loss(refined) -> (refined args f32, history f32 [steps]:
+    the loss before each step, kept on the device - the loop reads nothing back)"""
+    refined = args.detach().float().clone().requires_grad_(True)
+    opt = torch.optim.Adam([refined], lr=lr)
+    history = torch.empty(steps, dtype=torch.float32, device=refined.device)
+    for step in range(steps):
+        opt.zero_grad(set_to_none=True)
+        value = batch_loss(refined)
+        value.backward()
+        history[step] = value.detach()
+        opt.step()
+    return refined.detach(), history
+
+
 def sample_points(commands, args, n=10):
     """commands [N, S] -> one cloud per row; commands [N, G, S] -> one cloud per icon, its groups concatenated in order;
     args [..., S, 11].  float32 (as the dataset delivers them) and int64 (as greedy_sample returns them) are read as they
@@ -102,14 +149,7 @@ def sample_points(commands, args, n=10):
     end point shared with the next command once; a sequence with k drawing commands gives k (n - 1) + 1 points, one
     with none (an invisible group, where the reference raises) gives 0.  Rows past counts[i] are unspecified.
     float32 args that require grad (grad mode on) get their gradient through `points`; `counts` carries none."""
-    if commands.dim() not in (2, 3) or args.dim() != commands.dim() + 1 or args.shape[:-1] != commands.shape:
-        raise ValueError(f"sample_points: commands (N, S) or (N, G, S) with args (..., S, 11); got {tuple(commands.shape)} "
-                         f"and {tuple(args.shape)}")
-    if commands.dtype != args.dtype or commands.dtype not in (torch.float32, torch.int64):
-        commands, args = commands.float(), args.float()
-    groups = commands.shape[1] if commands.dim() == 3 else 1
-    S = commands.shape[-1]
-    commands, args = commands.reshape(-1, S).contiguous(), args.reshape(-1, S, args.shape[-1]).contiguous()
+    commands, args, groups = _flat_sequences("sample_points", commands, args)
     if args.dtype == torch.float32 and args.requires_grad and torch.is_grad_enabled():
         return _SamplePoints.apply(args, commands.detach(), n, groups)
     return ops.sample_points(commands, args, n=n, groups=groups)
@@ -130,19 +170,14 @@ def reconstruction_error(model, commands, args, label=None, n=10, temperature=0.
     as passed (SOS, EOS and padding give no points).  -> {"re": f32 [N], "valid": bool [N], "mean": 0-d}: `valid` where both
     clouds are non-empty, `re` NaN elsewhere, `mean` over the valid icons.  Runs without gradients in eval mode; the
     model's train / eval state is restored."""
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            commands_y, args_y = model.greedy_sample(commands, args, commands, args, label=label, concat_groups=False,
-                                                     temperature=temperature)
-            px, nx = sample_points(commands_y, args_y, n)
-            py, ny = sample_points(commands, args, n)
-            re = chamfer(px, nx, py, ny)
-            valid = (nx > 0) & (ny > 0)
-            mean = torch.where(valid, re, torch.zeros_like(re)).sum() / valid.sum()
-    finally:
-        model.train(was_training)
+    with _evaluating(model):
+        commands_y, args_y = model.greedy_sample(commands, args, commands, args, label=label, concat_groups=False,
+                                                 temperature=temperature)
+        px, nx = sample_points(commands_y, args_y, n)
+        py, ny = sample_points(commands, args, n)
+        re = chamfer(px, nx, py, ny)
+        valid = (nx > 0) & (ny > 0)
+        mean = _masked_mean(re, valid)
     return {"re": re, "valid": valid, "mean": mean}
 
 
@@ -156,8 +191,7 @@ def chamfer_loss(commands, args, target_points, target_counts, n=10):
     points, counts = sample_points(commands, args, n)
     per_icon = chamfer(points, counts, target_points, target_counts)
     valid = (counts > 0) & (target_counts > 0)
-    loss = torch.where(valid, per_icon, torch.zeros_like(per_icon)).sum() / valid.sum()
-    return {"loss": loss, "per_icon": per_icon, "valid": valid}
+    return {"loss": _masked_mean(per_icon, valid), "per_icon": per_icon, "valid": valid}
 
 
 def emd(points_x, counts_x, points_y, counts_y, first_point_weight=False, return_matched_indices=False):
@@ -182,8 +216,7 @@ def emd_loss(commands, args, target_points, target_counts, n=10, first_point_wei
     points, counts = sample_points(commands, args, n)
     per_icon = emd(points, counts, target_points, target_counts, first_point_weight)
     valid = (counts > 0) & (target_counts > 0)
-    loss = torch.where(valid, per_icon, torch.zeros_like(per_icon)).sum() / valid.sum()
-    return {"loss": loss, "per_icon": per_icon, "valid": valid}
+    return {"loss": _masked_mean(per_icon, valid), "per_icon": per_icon, "valid": valid}
 
 
 def polyline_length(points, counts):
@@ -225,13 +258,4 @@ def refine(commands, args, target_points, target_counts, steps=150, lr=0.1, n=10
     if loss not in _REFINE_LOSSES:
         raise ValueError(f"refine: loss {loss!r}, need one of {sorted(_REFINE_LOSSES)}")
     batch_loss = _REFINE_LOSSES[loss]
-    refined = args.detach().float().clone().requires_grad_(True)
-    opt = torch.optim.Adam([refined], lr=lr)
-    history = torch.empty(steps, dtype=torch.float32, device=refined.device)
-    for step in range(steps):
-        opt.zero_grad(set_to_none=True)
-        value = batch_loss(commands, refined, target_points, target_counts, n)["loss"]
-        value.backward()
-        history[step] = value.detach()
-        opt.step()
-    return refined.detach(), history
+    return _adam_refine(args, steps, lr, lambda refined: batch_loss(commands, refined, target_points, target_counts, n)["loss"])

@@ -8,6 +8,7 @@ import os
 import torch
 
 from . import lib as _l
+from .svgtensor import N_ARGS
 
 F32, BF16 = _l.DSVG_F32, _l.DSVG_BF16
 RELU = 1
@@ -1165,16 +1166,26 @@ def match_assign(cost, vis):
 # ------------------------------------------------------------------------------------------------
 # reconstruction error of decoded icons (difflib/tensor.py:191-230, difflib/loss.py:5-7) and its gradient
 # ------------------------------------------------------------------------------------------------
+def _chk_sequences(commands, args, groups, name=None):
+    """commands [B*groups, L] with args [B*groups, L, N_ARGS], both float32 or both int64; the backward wrappers (`name`)
+    pass float32 commands alone -> (B, L)"""
+    if args is None:
+        assert commands.dim() == 2 and commands.dtype == torch.float32 and commands.is_contiguous(), \
+            f"{name}: float32 commands [B*groups, L]"
+    else:
+        assert commands.dim() == 2 and args.dim() == 3 and args.shape[:2] == commands.shape and args.shape[2] == N_ARGS
+        assert commands.dtype == args.dtype and commands.dtype in (torch.float32, torch.int64)
+        assert commands.is_contiguous() and args.is_contiguous()
+    assert groups >= 1 and commands.shape[0] % groups == 0
+    return commands.shape[0] // groups, commands.shape[1]
+
+
 def sample_points(commands, args, n=10, groups=1):
     """commands [B*groups, L] / args [B*groups, L, 11], both float32 or both int64 (read as they are) ->
     points f32 [B, cap, 2] with cap = groups * (L * (n - 1) + 1), counts int32 [B]: n points per `l` / `c` command, the
     shared end points once, the `groups` sequences of a cloud concatenated; rows past counts[b] are not written"""
     _chk(commands, args)
-    assert commands.dim() == 2 and args.dim() == 3 and args.shape[:2] == commands.shape and args.shape[2] == 11
-    assert commands.dtype == args.dtype and commands.dtype in (torch.float32, torch.int64)
-    assert commands.is_contiguous() and args.is_contiguous()
-    assert groups >= 1 and commands.shape[0] % groups == 0
-    B, L = commands.shape[0] // groups, commands.shape[1]
+    B, L = _chk_sequences(commands, args, groups)
     points = torch.empty(B, groups * (L * (n - 1) + 1), 2, dtype=torch.float32, device=commands.device)
     counts = torch.empty(B, dtype=torch.int32, device=commands.device)
     _l.check(_l.load().dsvg_sample_points(F32 if commands.dtype == torch.float32 else _l.DSVG_I64, commands.data_ptr(),
@@ -1183,13 +1194,19 @@ def sample_points(commands, args, n=10, groups=1):
     return points, counts
 
 
+def _chk_cloud(p, n):
+    """p f32 [B, cap, 2] with n int32 [B] points in use -> (B, cap)"""
+    _chk(p, n)
+    assert p.dtype == torch.float32 and p.dim() == 3 and p.shape[2] == 2 and p.is_contiguous()
+    assert n.dtype == torch.int32 and n.shape == (p.shape[0],) and n.is_contiguous()
+    return p.shape[0], p.shape[1]
+
+
 def _chk_clouds(px, nx, py, ny):
     _chk(px, nx, py, ny)
-    for p, c in ((px, nx), (py, ny)):
-        assert p.dtype == torch.float32 and p.dim() == 3 and p.shape[2] == 2 and p.is_contiguous()
-        assert c.dtype == torch.int32 and c.shape == (p.shape[0],) and c.is_contiguous()
-    assert px.shape[0] == py.shape[0]
-    return px.shape[0], px.shape[1], py.shape[1]
+    (B, capx), (By, capy) = _chk_cloud(px, nx), _chk_cloud(py, ny)
+    assert B == By
+    return B, capx, capy
 
 
 def chamfer(px, nx, py, ny):
@@ -1240,13 +1257,10 @@ def sample_points_bwd(commands, dpoints, n=10, groups=1):
     """float32 commands [B*groups, L] and dpoints f32 [B, groups * (L * (n - 1) + 1), 2], laid out as sample_points returns
     its points -> dargs f32 [B*groups, L, 11], every element written (integer inputs have no gradient)"""
     _chk(commands, dpoints)
-    assert commands.dim() == 2 and commands.dtype == torch.float32 and commands.is_contiguous(), \
-        "sample_points_bwd: float32 commands [B*groups, L]"
-    assert groups >= 1 and commands.shape[0] % groups == 0
-    B, L = commands.shape[0] // groups, commands.shape[1]
+    B, L = _chk_sequences(commands, None, groups, "sample_points_bwd")
     assert dpoints.dtype == torch.float32 and dpoints.is_contiguous()
     assert dpoints.shape == (B, groups * (L * (n - 1) + 1), 2), f"sample_points_bwd: dpoints {tuple(dpoints.shape)}"
-    dargs = torch.empty(commands.shape[0], L, 11, dtype=torch.float32, device=commands.device)
+    dargs = torch.empty(commands.shape[0], L, N_ARGS, dtype=torch.float32, device=commands.device)
     _l.check(_l.load().dsvg_sample_points_bwd(commands.data_ptr(), B, groups, L, int(n), dpoints.data_ptr(),
                                               dargs.data_ptr(), _stream()), "dsvg_sample_points_bwd")
     return dargs
@@ -1275,9 +1289,7 @@ def emd_bwd(px, nx, ny, t, shift, dout, first_point_weight=False):
     """the pred clouds, the target counts and emd's `t` and `shift`, dout f32 [B] -> dpx f32 [B, capx, 2]: every row written,
     zeros past the counts and on icons with an empty cloud (whatever dout holds there); the target gets no gradient"""
     _chk(px, nx, ny, t, shift, dout)
-    assert px.dtype == torch.float32 and px.dim() == 3 and px.shape[2] == 2 and px.is_contiguous()
-    B, capx = px.shape[0], px.shape[1]
-    assert nx.dtype == torch.int32 and nx.shape == (B,) and nx.is_contiguous()
+    B, capx = _chk_cloud(px, nx)
     assert ny.dtype == torch.int32 and ny.shape == (B,) and ny.is_contiguous()
     assert t.dtype == torch.float32 and t.shape == (B, capx, 2) and t.is_contiguous()
     assert shift.dtype == torch.int32 and shift.shape == (B,) and shift.is_contiguous()
@@ -1287,13 +1299,6 @@ def emd_bwd(px, nx, ny, t, shift, dout, first_point_weight=False):
                                     dout.data_ptr(), int(bool(first_point_weight)), B, dpx.data_ptr(), _stream()),
              "dsvg_emd_bwd")
     return dpx
-
-
-def _chk_cloud(p, n):
-    _chk(p, n)
-    assert p.dtype == torch.float32 and p.dim() == 3 and p.shape[2] == 2 and p.is_contiguous()
-    assert n.dtype == torch.int32 and n.shape == (p.shape[0],) and n.is_contiguous()
-    return p.shape[0], p.shape[1]
 
 
 def polyline_length(p, n):
@@ -1323,6 +1328,24 @@ def polyline_length_bwd(p, n, dout):
 RASTER_CULL = True      # the default of raster_sweep's `cull`: faster on every configuration of profiles/raster_bench.log, same bits
 
 
+def _chord_cap(B, groups, L, n, fill):
+    """chord records per image as csrc/raster.hip sizes them (20 bytes each), at least 1: an n the call refuses gives 0"""
+    return max(_l.load().dsvg_raster_workspace_bytes(B, groups, L, int(n), int(bool(fill))) // (20 * B), 1)
+
+
+def _chk_records(segs, seg_counts):
+    """segs f32 [B, cap, 5] with seg_counts int32 [B] records in use -> (B, cap)"""
+    _chk(segs, seg_counts)
+    assert segs.dtype == torch.float32 and segs.dim() == 3 and segs.shape[2] == 5 and segs.is_contiguous()
+    assert seg_counts.dtype == torch.int32 and seg_counts.shape == (segs.shape[0],) and seg_counts.is_contiguous()
+    return segs.shape[0], segs.shape[1]
+
+
+def _raster_flags(fill, option, option_default, option_flag):
+    """the flags word of the sweeps: DSVG_RASTER_FILL and one option (`cull` or `wide`; None: the module default)"""
+    return (_l.DSVG_RASTER_FILL if fill else 0) | (option_flag if (option_default if option is None else option) else 0)
+
+
 def raster_segments(commands, args, n=10, groups=1, fill=False):
     """commands [B*groups, L] / args [B*groups, L, 11] as sample_points takes them -> (segs f32 [B, cap, 5], seg_counts int32
     [B]): the chords of image b in drawing order, n - 1 per `l` / `c` command and, with `fill`, one closing chord behind
@@ -1330,29 +1353,21 @@ def raster_segments(commands, args, n=10, groups=1, fill=False):
     by - ay and a flags word (view it as int32; bit 0: the first chord of a sequence; bits 1..: on a closing chord the number of
     records back to its sub-path's first chord).  Records past seg_counts[b] are not written"""
     _chk(commands, args)
-    assert commands.dim() == 2 and args.dim() == 3 and args.shape[:2] == commands.shape and args.shape[2] == 11
-    assert commands.dtype == args.dtype and commands.dtype in (torch.float32, torch.int64)
-    assert commands.is_contiguous() and args.is_contiguous()
-    assert groups >= 1 and commands.shape[0] % groups == 0 and commands.shape[0] >= groups
-    B, L = commands.shape[0] // groups, commands.shape[1]
-    lib = _l.load()
-    cap = lib.dsvg_raster_workspace_bytes(B, groups, L, int(n), int(bool(fill))) // (20 * B)      # (0 for an n the call refuses)
-    segs = torch.empty(B, max(cap, 1), 5, dtype=torch.float32, device=commands.device)
+    B, L = _chk_sequences(commands, args, groups)
+    assert B >= 1
+    segs = torch.empty(B, _chord_cap(B, groups, L, n, fill), 5, dtype=torch.float32, device=commands.device)
     seg_counts = torch.empty(B, dtype=torch.int32, device=commands.device)
-    _l.check(lib.dsvg_raster_segments(F32 if commands.dtype == torch.float32 else _l.DSVG_I64, commands.data_ptr(),
-                                      args.data_ptr(), B, groups, L, int(n), int(bool(fill)), segs.data_ptr(),
-                                      segs.numel() * 4, seg_counts.data_ptr(), _stream()), "dsvg_raster_segments")
+    _l.check(_l.load().dsvg_raster_segments(F32 if commands.dtype == torch.float32 else _l.DSVG_I64, commands.data_ptr(),
+                                            args.data_ptr(), B, groups, L, int(n), int(bool(fill)), segs.data_ptr(),
+                                            segs.numel() * 4, seg_counts.data_ptr(), _stream()), "dsvg_raster_segments")
     return segs, seg_counts
 
 
 def raster_sweep(segs, seg_counts, size=64, stroke_width=3.2, fill=False, cull=None):
     """the records of raster_segments (built with the same `fill`) -> f32 [B, size, size], 1 = ink: stroke or fill coverage as
     include/dsvg.h defines it.  `cull` (None: RASTER_CULL) skips chords out of a wave's reach; the image has the same bits"""
-    _chk(segs, seg_counts)
-    assert segs.dtype == torch.float32 and segs.dim() == 3 and segs.shape[2] == 5 and segs.is_contiguous()
-    assert seg_counts.dtype == torch.int32 and seg_counts.shape == (segs.shape[0],) and seg_counts.is_contiguous()
-    B, cap = segs.shape[0], segs.shape[1]
-    flags = (_l.DSVG_RASTER_FILL if fill else 0) | (_l.DSVG_RASTER_CULL if (RASTER_CULL if cull is None else cull) else 0)
+    B, cap = _chk_records(segs, seg_counts)
+    flags = _raster_flags(fill, cull, RASTER_CULL, _l.DSVG_RASTER_CULL)
     out = torch.empty(B, int(size), int(size), dtype=torch.float32, device=segs.device)
     _l.check(_l.load().dsvg_raster_sweep(segs.data_ptr(), seg_counts.data_ptr(), B, cap, int(size), float(stroke_width),
                                          flags, out.data_ptr(), _stream()), "dsvg_raster_sweep")
@@ -1369,19 +1384,12 @@ RASTER_BWD_WIDE = False      # the default of raster_sweep_bwd's `wide`: 16 lane
                              # configurations of profiles/raster_grad_bench.log (a wave per chord wins at fill, 128 pixels)
 
 
-def _chk_records(segs, seg_counts):
-    _chk(segs, seg_counts)
-    assert segs.dtype == torch.float32 and segs.dim() == 3 and segs.shape[2] == 5 and segs.is_contiguous()
-    assert seg_counts.dtype == torch.int32 and seg_counts.shape == (segs.shape[0],) and seg_counts.is_contiguous()
-    return segs.shape[0], segs.shape[1]
-
-
 def raster_sweep_nn(segs, seg_counts, size=64, stroke_width=3.2, fill=False, cull=None):
     """raster_sweep that also returns the arg-min -> (out f32 [B, size, size] with raster_sweep's bits, idx int32 [B, size,
     size]: the record index of the pixel's nearest chord where 0 < out < 1 (ties go to the lowest index), -1 everywhere
     else); idx is the same with and without `cull`"""
     B, cap = _chk_records(segs, seg_counts)
-    flags = (_l.DSVG_RASTER_FILL if fill else 0) | (_l.DSVG_RASTER_CULL if (RASTER_CULL if cull is None else cull) else 0)
+    flags = _raster_flags(fill, cull, RASTER_CULL, _l.DSVG_RASTER_CULL)
     out = torch.empty(B, int(size), int(size), dtype=torch.float32, device=segs.device)
     idx = torch.empty(B, int(size), int(size), dtype=torch.int32, device=segs.device)
     _l.check(_l.load().dsvg_raster_sweep_nn(segs.data_ptr(), seg_counts.data_ptr(), B, cap, int(size), float(stroke_width),
@@ -1399,7 +1407,7 @@ def raster_sweep_bwd(segs, seg_counts, out, idx, dout, stroke_width=3.2, fill=Fa
     assert out.dtype == torch.float32 and out.shape == (B, size, size) and out.is_contiguous()
     assert idx.dtype == torch.int32 and idx.shape == out.shape and idx.is_contiguous()
     assert dout.dtype == torch.float32 and dout.shape == out.shape and dout.is_contiguous()
-    flags = (_l.DSVG_RASTER_FILL if fill else 0) | (_l.DSVG_RASTER_WIDE if (RASTER_BWD_WIDE if wide is None else wide) else 0)
+    flags = _raster_flags(fill, wide, RASTER_BWD_WIDE, _l.DSVG_RASTER_WIDE)
     dsegs = torch.empty(B, cap, 4, dtype=torch.float32, device=segs.device)
     _l.check(_l.load().dsvg_raster_sweep_bwd(segs.data_ptr(), seg_counts.data_ptr(), out.data_ptr(), idx.data_ptr(),
                                              dout.data_ptr(), B, cap, size, float(stroke_width), flags, dsegs.data_ptr(),
@@ -1412,18 +1420,15 @@ def raster_segments_bwd(commands, dsegs, seg_counts, n=10, groups=1, fill=False)
     raster_segments (same n, groups, fill) -> dargs f32 [B*groups, L, 11], every element written (integer inputs have no
     gradient)"""
     _chk(commands, dsegs, seg_counts)
-    assert commands.dim() == 2 and commands.dtype == torch.float32 and commands.is_contiguous(), \
-        "raster_segments_bwd: float32 commands [B*groups, L]"
-    assert groups >= 1 and commands.shape[0] % groups == 0 and commands.shape[0] >= groups
-    B, L = commands.shape[0] // groups, commands.shape[1]
-    lib = _l.load()
-    cap = lib.dsvg_raster_workspace_bytes(B, groups, L, int(n), int(bool(fill))) // (20 * B)      # (0 for an n the call refuses)
-    assert dsegs.dtype == torch.float32 and dsegs.shape == (B, max(cap, 1), 4) and dsegs.is_contiguous(), \
+    B, L = _chk_sequences(commands, None, groups, "raster_segments_bwd")
+    assert B >= 1
+    assert dsegs.dtype == torch.float32 and dsegs.shape == (B, _chord_cap(B, groups, L, n, fill), 4) and dsegs.is_contiguous(), \
         f"raster_segments_bwd: dsegs {tuple(dsegs.shape)}"
     assert seg_counts.dtype == torch.int32 and seg_counts.shape == (B,) and seg_counts.is_contiguous()
-    dargs = torch.empty(commands.shape[0], L, 11, dtype=torch.float32, device=commands.device)
-    _l.check(lib.dsvg_raster_segments_bwd(commands.data_ptr(), dsegs.data_ptr(), seg_counts.data_ptr(), B, groups, L, int(n),
-                                          int(bool(fill)), dargs.data_ptr(), _stream()), "dsvg_raster_segments_bwd")
+    dargs = torch.empty(commands.shape[0], L, N_ARGS, dtype=torch.float32, device=commands.device)
+    _l.check(_l.load().dsvg_raster_segments_bwd(commands.data_ptr(), dsegs.data_ptr(), seg_counts.data_ptr(), B, groups, L,
+                                                int(n), int(bool(fill)), dargs.data_ptr(), _stream()),
+             "dsvg_raster_segments_bwd")
     return dargs
 
 
@@ -1436,14 +1441,14 @@ def canonicalize(commands, args, g_out, s_out, concat=False, numericalize=0):
     "n_groups" int32 [N], "len_groups" / "source_group" int32 [N, g_out], "reversed" bool [N, g_out], "valid" bool [N].
     One launch, no workspace; include/dsvg.h has the definition"""
     _chk(commands, args)
-    assert commands.dim() == 3 and args.dim() == 4 and args.shape[:3] == commands.shape and args.shape[3] == 11
+    assert commands.dim() == 3 and args.dim() == 4 and args.shape[:3] == commands.shape and args.shape[3] == N_ARGS
     assert commands.dtype == args.dtype and commands.dtype in (torch.float32, torch.int64)
     assert commands.is_contiguous() and args.is_contiguous()
     N, G, S = commands.shape
     dev = commands.device
     rows = (int(s_out),) if concat else (int(g_out), int(s_out))
     out_c = torch.empty((N,) + rows, dtype=commands.dtype, device=dev)
-    out_a = torch.empty((N,) + rows + (11,), dtype=commands.dtype, device=dev)
+    out_a = torch.empty((N,) + rows + (N_ARGS,), dtype=commands.dtype, device=dev)
     n_groups = torch.empty(N, dtype=torch.int32, device=dev)
     len_groups = torch.empty(N, int(g_out), dtype=torch.int32, device=dev)
     source_group = torch.empty(N, int(g_out), dtype=torch.int32, device=dev)

@@ -29,6 +29,7 @@ an arg-min saved by the forward: no atomics, bit-reproducible.
 import torch
 
 from . import ops
+from .metrics import _adam_refine, _evaluating, _flat_sequences
 
 __all__ = ["rasterize", "rasterize_with_grad", "image_loss", "refine_to_images", "reconstruction_images", "interpolate",
            "interpolation_alphas"]
@@ -47,15 +48,7 @@ def rasterize(commands, args, size=64, stroke_width=3.2, fill=False, n=10):
         layers = rasterize(commands.reshape(N * G, S), args.reshape(N * G, S, 11), fill=True).view(N, G, 1, size, size)
         rgb = 1 - (layers * (1 - torch.rand(N, G, 3, 1, 1, device=layers.device))).amax(1)          # [N, 3, size, size]
     """
-    if commands.dim() not in (2, 3) or args.dim() != commands.dim() + 1 or args.shape[:-1] != commands.shape:
-        raise ValueError(f"rasterize: commands (N, S) or (N, G, S) with args (..., S, 11); got {tuple(commands.shape)} "
-                         f"and {tuple(args.shape)}")
-    commands, args = commands.detach(), args.detach()
-    if commands.dtype != args.dtype or commands.dtype not in (torch.float32, torch.int64):
-        commands, args = commands.float(), args.float()
-    groups = commands.shape[1] if commands.dim() == 3 else 1
-    S = commands.shape[-1]
-    commands, args = commands.reshape(-1, S).contiguous(), args.reshape(-1, S, args.shape[-1]).contiguous()
+    commands, args, groups = _flat_sequences("rasterize", commands.detach(), args.detach())
     return ops.rasterize(commands, args, size=size, stroke_width=stroke_width, fill=fill, n=n, groups=groups)
 
 
@@ -84,15 +77,10 @@ def rasterize_with_grad(commands, args, size=64, stroke_width=3.2, fill=False, n
     """`rasterize` for float32 `args` that receive a gradient: the same shapes, the same image bit for bit, and
     d image / d args flows back (module docstring: formulas and conventions).  `commands` of any dtype are read as float32;
     the backward is not differentiable again."""
-    if commands.dim() not in (2, 3) or args.dim() != commands.dim() + 1 or args.shape[:-1] != commands.shape:
-        raise ValueError(f"rasterize_with_grad: commands (N, S) or (N, G, S) with args (..., S, 11); got "
-                         f"{tuple(commands.shape)} and {tuple(args.shape)}")
+    commands, flat_args, groups = _flat_sequences("rasterize_with_grad", commands.detach(), args)
     if args.dtype != torch.float32:
         raise ValueError(f"rasterize_with_grad: float32 args (integer arguments have no gradient); got {args.dtype}")
-    groups = commands.shape[1] if commands.dim() == 3 else 1
-    S = commands.shape[-1]
-    commands, args = commands.detach().float().reshape(-1, S).contiguous(), args.reshape(-1, S, args.shape[-1]).contiguous()
-    return _Rasterize.apply(commands, args, int(size), float(stroke_width), bool(fill), int(n), groups)
+    return _Rasterize.apply(commands, flat_args, int(size), float(stroke_width), bool(fill), int(n), groups)
 
 
 def image_loss(commands, args, target_images, **raster):
@@ -120,18 +108,14 @@ def refine_to_images(commands, args, target_images, steps=150, lr=0.1, **raster)
     targets = [target_images] if torch.is_tensor(target_images) else list(target_images)
     if not targets:
         raise ValueError("refine_to_images: no target images")
-    refined = args.detach().float().clone().requires_grad_(True)
-    opt = torch.optim.Adam([refined], lr=lr)
-    history = torch.empty(steps, dtype=torch.float32, device=refined.device)
-    for step in range(steps):
-        opt.zero_grad(set_to_none=True)
+
+    def batch_loss(refined):
         value = image_loss(commands, refined, targets[0], **raster)["loss"]
         for target in targets[1:]:
             value = value + image_loss(commands, refined, target, **raster)["loss"]
-        value.backward()
-        history[step] = value.detach()
-        opt.step()
-    return refined.detach(), history
+        return value
+
+    return _adam_refine(args, steps, lr, batch_loss)
 
 
 def reconstruction_images(model, commands, args, label=None, size=64, temperature=0.0, **raster):
@@ -139,16 +123,11 @@ def reconstruction_images(model, commands, args, label=None, size=64, temperatur
     gradients, ``concat_groups=False``) and draw the decoded icons next to the targets, taken exactly as passed.
     -> {"decoded": f32 [N, size, size], "target": f32 [N, size, size]}.  `raster`: stroke_width, fill, n of `rasterize`.
     The model's train / eval state is restored."""
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            commands_y, args_y = model.greedy_sample(commands, args, commands, args, label=label, concat_groups=False,
-                                                     temperature=temperature)
-            decoded = rasterize(commands_y, args_y, size=size, **raster)
-            target = rasterize(commands, args, size=size, **raster)
-    finally:
-        model.train(was_training)
+    with _evaluating(model):
+        commands_y, args_y = model.greedy_sample(commands, args, commands, args, label=label, concat_groups=False,
+                                                 temperature=temperature)
+        decoded = rasterize(commands_y, args_y, size=size, **raster)
+        target = rasterize(commands, args, size=size, **raster)
     return {"decoded": decoded, "target": target}
 
 
@@ -176,14 +155,9 @@ def interpolate(model, z1, z2, steps=25, ease=True, label=None, size=64, tempera
     z = ((1 - a) * za + a * zb).reshape(N * steps, 1, 1, dim_z)
     if label is not None:
         label = label.repeat_interleave(steps, dim=0)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            commands_y, args_y = model.greedy_sample(None, None, None, None, label=label, z=z, concat_groups=False,
-                                                     temperature=temperature)
-            frames = rasterize(commands_y, args_y, size=size, **raster)
-    finally:
-        model.train(was_training)
+    with _evaluating(model):
+        commands_y, args_y = model.greedy_sample(None, None, None, None, label=label, z=z, concat_groups=False,
+                                                 temperature=temperature)
+        frames = rasterize(commands_y, args_y, size=size, **raster)
     return {"frames": frames.view(N, steps, size, size), "commands": commands_y.reshape(N, steps, *commands_y.shape[1:]),
             "args": args_y.reshape(N, steps, *args_y.shape[1:])}

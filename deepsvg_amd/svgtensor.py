@@ -19,6 +19,8 @@ CMD_ARGS_MASK = torch.tensor([[0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1],   # m
                               [0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0],   # SOS
                               [0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0]])  # z
 
+N_ARGS = CMD_ARGS_MASK.shape[1]      # 11 argument columns per command
+
 PAD_VAL = -1
 
 

@@ -4,7 +4,9 @@ added variant left the code AND the resources of the existing kernels untouched.
 function, kernel or file that one side lacks.
 usage: scripts/isa_all.sh old_dir   (on the old tree)    scripts/isa_all.sh new_dir   (on the new tree)
        python scripts/isa_diff.py old_dir new_dir        every *.s of both directories, paired by name, a report per file
-       python scripts/isa_diff.py old.s new.s            one pair of files"""
+       python scripts/isa_diff.py old.s new.s            one pair of files
+       ... --rename OLD=NEW                              (repeatable) a kernel whose mangled name changed on purpose is compared
+                                                         under its new name; a kernarg size that differs is reported, not counted"""
 import os
 import re
 import sys
@@ -46,9 +48,20 @@ def funcs(path):
     return out, res
 
 
+RENAMES = {}
+
+
 def diff_files(pa, pb):
     (a, ra), (b, rb) = funcs(pa), funcs(pb)
     bad = 0
+    for old, new in RENAMES.items():
+        if old in a and new in b:
+            print(f"{'renamed':10s} {old}\n{'':10s} -> {new}")
+            a = {new if k == old else k: ([t.replace(old, new) for t in v] if k == old else v) for k, v in a.items()}
+            ra[new] = ra.pop(old)
+            if ra[new].get("kernarg_size") != rb[new].get("kernarg_size"):
+                print(f"{'':10s} kernarg_size: {ra[new].get('kernarg_size')} -> {rb[new].get('kernarg_size')} (allowed under --rename)")
+                ra[new]["kernarg_size"] = rb[new].get("kernarg_size")
     for k in a:
         same = a[k] == b.get(k)
         bad += not same
@@ -94,4 +107,10 @@ def main(pa, pb):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    argv = sys.argv[1:]
+    while "--rename" in argv:
+        i = argv.index("--rename")
+        old, new = argv[i + 1].split("=")
+        RENAMES[old] = new
+        del argv[i:i + 2]
+    sys.exit(main(argv[0], argv[1]))

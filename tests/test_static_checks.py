@@ -79,3 +79,38 @@ def test_mfma_operand_layout_is_stated_once():
     kept = {"gemm.hip": 2, "gemm_bf16.hip": 2}
     formula = r"\(\s*(\w+)\s*&\s*3\s*\)\s*\+\s*8\s*\*\s*\(\s*\1\s*>>\s*2\s*\)\s*\+\s*4\s*\*"
     assert where(lambda t: len(re.findall(formula, t))) == {"mfma_frag.h": 1, **kept}
+
+
+def test_geometry_tier_is_stated_once():
+    """The token layout, the flag scan and the curve math are a contract between sample_points, the rasteriser, their
+    backwards and the canonical path order (csrc/svg_seq.h): one definition of each in csrc, and one Chamfer sweep and slice
+    kernel under a template flag.  Finds duplication only; scripts/isa_diff.py checks the code
+    (profiles/geometry_header_isa.log)."""
+    code = _csrc_code()
+    where = lambda count: {f: count(t) for f, t in code.items() if count(t)}
+    hdr = {"svg_seq.h": 1}
+    # the scan (under any prefix), its three flags, the count clamp, the start point
+    assert where(lambda t: len(re.findall(r"\b\w*flag_scan\s*\([^;{]*\)\s*\{", t))) == hdr
+    for name in ("is_drawing", "sequence_draws", "subpath_ends", "chamfer_count", "start_point", "sequence_args_ok"):
+        assert where(lambda t: _definitions(t, name)) == hdr, name
+    clamp = r"min\s*\(\s*\(long long\)\s*max\s*\(\s*\w+\s*\[\s*\w+\s*\]\s*,\s*0\s*\)\s*,\s*\w+\s*\)"
+    assert where(lambda t: len(re.findall(clamp, t))) == hdr
+    # the power basis with its Horner evaluation, and the backward accumulator with its row store
+    assert where(lambda t: len(re.findall(r"\bstruct\s+CubicPower\s*\{", t))) == hdr
+    assert where(lambda t: len(re.findall(r"\bstruct\s+ArgRowGrad\s*\{", t))) == hdr
+    horner = r"fmaf\s*\(\s*fmaf\s*\(\s*fmaf\s*\(\s*c3x\s*,"
+    assert where(lambda t: len(re.findall(horner, t))) == hdr
+    # Kept apart, by name and count: hipcc orders raster_segments_kernel and raster_segments_bwd_kernel differently with
+    # start_point's two selects and with the struct (or its updates as functions), so raster.hip keeps its one-branch start
+    # point and the accumulator written out (the Bernstein weights and the row store once more)
+    bernstein = r"3\.0\s*\*\s*w\s*\*\s*w\s*\*\s*z"
+    assert where(lambda t: len(re.findall(bernstein, t))) == {**hdr, "raster.hip": 1}
+    assert where(lambda t: len(re.findall(r"\brow\s*\[\s*\w+\s*\]\s*=\s*\(float\)\s*c1x", t))) == {**hdr, "raster.hip": 1}
+    assert where(lambda t: len(re.findall(r"\?\s*make_float2\s*\([^;]*-\s*N_ARGS\s*\]", t))) == {"raster.hip": 1}
+    # one Chamfer sweep and one slice kernel
+    assert where(lambda t: len(re.findall(r"\bvoid\s+chamfer_sweep\w*\s*\(", t))) == {"metrics.hip": 1}
+    assert where(lambda t: len(re.findall(r"\bvoid\s+chamfer\w*_slice_kernel\s*\(", t))) == {"metrics.hip": 1}
+    # the vocabulary: the argument count and the `l` / `c` ids, under any name
+    assert where(lambda t: len(re.findall(r"\bconstexpr\s+int\s+[^;]*\bN_ARGS\s*=", t))) == hdr
+    ids = r"\bconstexpr\s+int\s+[^;]*\b\w*L\s*=\s*1\s*,\s*\w*C\s*=\s*2\b"
+    assert where(lambda t: len(re.findall(ids, t))) == hdr
