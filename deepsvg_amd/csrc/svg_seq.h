@@ -1,8 +1,9 @@
 // Sequences of drawing commands on the device, stated once for csrc/metrics.hip (sample_points and its backward),
-// csrc/raster.hip (the chords of an image and their backward), csrc/paths.hip (canonical path order) and
-// csrc/assemble.hip (batch assembly): the command vocabulary and the argument columns of SVGTensor
-// (deepsvg/difflib/tensor.py:8-41), the ballot prefix scan that gives every drawing command its output offset and the
-// scans built on it, the count clamp of a cloud, and the curve a drawing command draws with its transpose.
+// csrc/raster.hip (the chords of an image and their backward), csrc/paths.hip (canonical path order),
+// csrc/paths_expand.hip (commands split, arcs converted) and csrc/assemble.hip (batch assembly): the command vocabulary
+// and the argument columns of SVGTensor (deepsvg/difflib/tensor.py:8-41), the ballot prefix scan that gives every drawing
+// command its output offset and the scans built on it, the prefix sum of counts for rows that become several, the count
+// clamp of a cloud, and the curve a drawing command draws with its transpose.
 //
 // The contracts that live here: the rasteriser's vertices are sample_points' points, and the backward kernels run on the
 // forward's offsets.  A drawing command (`l`, `c`) of token t starts at the end position of the row before it, whatever that
@@ -54,6 +55,49 @@ __device__ __forceinline__ void block_flag_scan(int n, C* __restrict__ pre, int*
                 int tot = base;
                 for (int q = w; q < n_chunks * (SP_THREADS / 64); ++q) tot += wtot[q];
                 pre[n] = (C)tot;
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// Exclusive prefix SUM of a non-negative count by one workgroup of SP_THREADS threads, for the kernels where an item becomes
+// 0..k output rows (csrc/paths_expand.hip): an inclusive shuffle scan per wave and chunk, then the prefix over the wave totals
+// as above.  pre[t] = sum of count(i) over items i < t, for t in 0..n (pre[n] = the total); the caller keeps n times the
+// largest count below 2^31.  count(t) is called by every thread for t < the chunk-rounded n and must return 0 past n.
+template <int MAXT, typename F>
+__device__ __forceinline__ void block_count_sum(int n, int* __restrict__ pre, int* __restrict__ wtot, F count) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n_chunks = (n + SP_THREADS - 1) / SP_THREADS;
+    int below[MAXT / SP_THREADS];           // counts below this lane inside its wave, per chunk (unrolled: registers)
+#pragma unroll
+    for (int c = 0; c < MAXT / SP_THREADS; ++c) {
+        below[c] = 0;
+        if (c < n_chunks) {
+            const int v = count(c * SP_THREADS + tid);
+            int inc = v;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int up = __shfl_up(inc, d, 64);
+                if (lane >= d) inc += up;
+            }
+            below[c] = inc - v;
+            if (lane == 63) wtot[c * (SP_THREADS / 64) + wave] = inc;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < MAXT / SP_THREADS; ++c) {
+        if (c < n_chunks) {
+            const int w = c * (SP_THREADS / 64) + wave;
+            int base = 0;
+            for (int q = 0; q < w; ++q) base += wtot[q];
+            const int t = c * SP_THREADS + tid;
+            if (t < n) pre[t] = base + below[c];
+            if (t == n - 1) {
+                int tot = base;
+                for (int q = w; q < n_chunks * (SP_THREADS / 64); ++q) tot += wtot[q];
+                pre[n] = tot;
             }
         }
     }

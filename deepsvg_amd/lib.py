@@ -14,6 +14,7 @@ DSVG_F32 = 0
 DSVG_BF16 = 1
 DSVG_I64 = 2          # input dtype of dsvg_sample_points / dsvg_raster_segments / dsvg_canonicalize only
 DSVG_PATHS_GROUPED, DSVG_PATHS_CONCAT = 0, 1   # layouts of dsvg_canonicalize
+DSVG_EXPAND_SPLIT, DSVG_EXPAND_ARCS = 0, 1     # modes of dsvg_paths_expand
 DSVG_RASTER_FILL, DSVG_RASTER_CULL = 1, 2      # flags of dsvg_raster_sweep
 DSVG_RASTER_WIDE = 4                           # flag of dsvg_raster_sweep_bwd: a wave per chord, not 16 lanes
 # == DSVG_ABI_VERSION of include/dsvg.h at the time SIGNATURES below was written: load() refuses a library built from another
@@ -173,6 +174,7 @@ SIGNATURES = {
     "dsvg_raster_sweep_bwd": (c_i32, [vp, vp, vp, vp, vp, c_i64, c_i64, c_i32, c_f32, c_i32, vp, vp]),
     "dsvg_raster_segments_bwd": (c_i32, [vp, vp, vp, c_i64, c_i32, c_i32, c_i32, c_i32, vp, vp]),
     "dsvg_canonicalize": (c_i32, [c_i32, vp, vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "dsvg_paths_expand": (c_i32, [c_i32, vp, vp, c_i64, c_i32, c_i32, c_i32, c_i32, C.c_double, c_i32, vp, vp, vp, vp, vp, vp, vp]),
     "dsvg_ffn_pack_bytes": (c_i64, [c_i32, c_i32]),
     "dsvg_ffn_pack": (c_i32, [vp, vp, c_i32, c_i32, c_i32, vp, vp, vp, vp, vp]),
     "dsvg_ffn_fwd": (c_i32, [vp, vp, vp, vp, vp, vp, vp, vp, c_i64, c_f32, c_f32, c_u32, c_u32, vp, c_i32, vp]),

@@ -1464,6 +1464,34 @@ def canonicalize(commands, args, g_out, s_out, concat=False, numericalize=0):
             "reversed": rev, "valid": valid}
 
 
+def paths_expand(commands, args, s_out, arcs=False, n=0, max_dist=0.0, include_lines=True):
+    """commands [N, G, S] / args [N, G, S, 11] float32, G * S <= 2048 and G * s_out <= 2048 -> the dict of
+    deepsvg_amd.paths.split (n >= 1, or n = 0 with max_dist > 0) or, with arcs=True, of deepsvg_amd.paths.arcs_to_beziers:
+    "commands" [N, G, s_out], "args" [N, G, s_out, 11] float32, "len_groups" int32 [N, G], "source_row" int32 [N, G, s_out],
+    "valid" bool [N] and, for split, "lengths" float32 [N, G, S].  One launch, no workspace; include/dsvg.h has the definition"""
+    _chk(commands, args)
+    assert commands.dim() == 3 and args.dim() == 4 and args.shape[:3] == commands.shape and args.shape[3] == N_ARGS
+    assert commands.dtype == args.dtype == torch.float32 and commands.is_contiguous() and args.is_contiguous()
+    N, G, S = commands.shape
+    dev = commands.device
+    s_out = int(s_out)
+    out_c = torch.empty(N, G, s_out, dtype=torch.float32, device=dev)
+    out_a = torch.empty(N, G, s_out, N_ARGS, dtype=torch.float32, device=dev)
+    len_groups = torch.empty(N, G, dtype=torch.int32, device=dev)
+    source_row = torch.empty(N, G, s_out, dtype=torch.int32, device=dev)
+    valid = torch.empty(N, dtype=torch.bool, device=dev)
+    lengths = None if arcs else torch.empty(N, G, S, dtype=torch.float32, device=dev)
+    _l.check(_l.load().dsvg_paths_expand(_l.DSVG_EXPAND_ARCS if arcs else _l.DSVG_EXPAND_SPLIT, commands.data_ptr(),
+                                         args.data_ptr(), N, G, S, s_out, int(n), float(max_dist), int(bool(include_lines)),
+                                         out_c.data_ptr(), out_a.data_ptr(), len_groups.data_ptr(), source_row.data_ptr(),
+                                         None if arcs else lengths.data_ptr(), valid.data_ptr(), _stream()),
+             "dsvg_paths_expand")
+    res = {"commands": out_c, "args": out_a, "len_groups": len_groups, "source_row": source_row, "valid": valid}
+    if not arcs:
+        res["lengths"] = lengths
+    return res
+
+
 # ------------------------------------------------------------------------------------------------
 # device-side batch assembly (svgtensor_dataset.py:164-205)
 # ------------------------------------------------------------------------------------------------

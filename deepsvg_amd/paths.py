@@ -30,13 +30,23 @@ The definition (include/dsvg.h; tests/paths_ref.py restates it in float64):
     ``Point.numericalize`` (svglib/geom.py:182-183) without the view-box rescale of ``SVG.numericalize``: arguments are taken
     to be in the 0..256 box already, as everywhere in this package.
 The op is not idempotent in general (steps 4 and 5).  Arcs are out of scope, as in `metrics.sample_points` and the rasteriser.
+`arcs_to_beziers` below removes them first: it turns every `a` into `c` rows, after which all three accept the icon.
+
+`split` and `arcs_to_beziers` are the two steps of the reference's preprocessing chain in which a command becomes several
+(``SVGPath.split``, svglib/svg_path.py:615-630, first and last step of ``simplify_heuristic``; ``SVGPath.simplify_arcs``,
+svg_path.py:280-293): one launch of csrc/paths_expand.hip for the whole batch.  include/dsvg.h has their definition,
+tests/paths_expand_ref.py restates it in float64.  The chain back into the model is
+``arcs_to_beziers -> split(max_dist=7.5 * 256 / 24) -> canonicalize(numericalize=256)``; only the Bezier fit between the
+reference's two splits (``SVGPath.simplify``) stays on the host.
 """
+import math
+
 import torch
 
 from . import ops
 from .svgtensor import CMD_ARGS_MASK, C_ID
 
-__all__ = ["canonicalize", "numericalize"]
+__all__ = ["canonicalize", "numericalize", "split", "arcs_to_beziers"]
 
 MAX_ROWS = 2048      # G * S rows per icon: the largest icon the model accepts in a two-stage config, 8 groups of 256
 
@@ -85,6 +95,78 @@ def canonicalize(commands, args, max_num_groups=None, max_seq_len=None, layout="
         commands, args = commands.float(), args.float()
     return ops.canonicalize(commands.contiguous(), args.contiguous(), g_out, s_out, concat=layout == "concat",
                             numericalize=0 if numericalize is None else int(numericalize))
+
+
+def _expand(name, commands, args, max_seq_len, **mode):
+    """the argument checks and the launch `split` and `arcs_to_beziers` share"""
+    if commands.dim() not in (2, 3) or args.dim() != commands.dim() + 1 or args.shape[:-1] != commands.shape \
+            or args.shape[-1] != 11:
+        raise ValueError(f"{name}: commands (N, G, S) with args (N, G, S, 11), or (N, S) with (N, S, 11); got "
+                         f"{tuple(commands.shape)} and {tuple(args.shape)}")
+    squeeze = commands.dim() == 2
+    if squeeze:
+        commands, args = commands.unsqueeze(1), args.unsqueeze(1)
+    N, G, S = commands.shape
+    if N < 1:
+        raise ValueError(f"{name}: an empty batch")
+    if max_seq_len is not None and int(max_seq_len) < 0:
+        raise ValueError(f"{name}: max_seq_len >= 0; got {max_seq_len}")
+    s_out = S if max_seq_len is None else int(max_seq_len) + 2
+    if S < 2 or G * S > MAX_ROWS or G * s_out > MAX_ROWS:
+        raise ValueError(f"{name}: {G} x {S} rows per icon in, {G} x {s_out} out; at least 2 per group and at most {MAX_ROWS} "
+                         f"per icon")
+    res = ops.paths_expand(commands.detach().float().contiguous(), args.detach().float().contiguous(), s_out, **mode)
+    if squeeze:
+        res = {k: (v if k == "valid" else v.squeeze(1)) for k, v in res.items()}
+    return res
+
+
+def split(commands, args, n=None, max_dist=None, include_lines=True, max_seq_len=None):
+    """``SVGPath.split`` for a batch: every `l` (unless include_lines=False) and `c` becomes k rows that draw the same curve,
+    k = n, or max(ceil(length / max_dist), 1) with the length of an `l` its chord and of a `c` the polyline through its 100
+    points at z = i / 99 (``SVGCommandBezier.length``).  Exactly one of n (int >= 1) and max_dist (finite, > 0) is given.
+    commands (N, G, S) with args (N, G, S, 11), or (N, S) with (N, S, 11) read as G = 1 (the group axis is squeezed away again
+    in the result); G * S <= 2048 and G * S_out <= 2048.  Inputs are detached and read as float32.  -> a dict, float32, no
+    gradient:
+      "commands" (N, G, S_out), "args" (N, G, S_out, 11), S_out = max_seq_len + 2 (default S): SOS, the rows, EOS to the end;
+        every slot CMD_ARGS_MASK does not enable is -1.  Row 0 of a group is its frame and is never read as a command; a group
+        ends at its first EOS.  An `l` gives ends at (1 - a) p0 + a p1, a = (i + 1) / k; a `c` the sub-curves on [i / k,
+        (i + 1) / k].  Float64 throughout, rounded to float32 once; the last piece carries the row's end position bit for bit,
+        and as the layout stores no start points consecutive pieces join exactly.  m, z and rows with k = 1 pass through.
+      "len_groups" int32 (N, G): rows between SOS and the first EOS; "source_row" int32 (N, G, S_out): the input row (index
+        in its group) an output row came from, -1 on SOS, EOS and padding; "lengths" float32 (N, G, S): the length of every
+        live `l` / `c`, 0 elsewhere; "valid" bool (N,).
+    An icon is invalid when a group needs more than S_out - 2 rows, when it holds a live `a` (the reference raises; see
+    `arcs_to_beziers`), a command outside the vocabulary, or a live `l` / `c` whose start, arguments or length is not finite.
+    It comes back as SOS, EOS... in every group with len_groups = 0, as `canonicalize` hands back an invalid icon.  n = 1, or
+    max_dist above every length, is the identity on valid icons."""
+    if (n is None) == (max_dist is None):
+        raise ValueError(f"split: exactly one of n and max_dist; got n={n!r} and max_dist={max_dist!r}")
+    if n is not None and (isinstance(n, bool) or not isinstance(n, int) or n < 1):
+        raise ValueError(f"split: n is an int >= 1; got {n!r}")
+    if max_dist is not None:
+        if isinstance(max_dist, bool) or not isinstance(max_dist, (int, float)) or not math.isfinite(max_dist) or max_dist <= 0:
+            raise ValueError(f"split: max_dist is finite and > 0; got {max_dist!r}")
+    return _expand("split", commands, args, max_seq_len, n=0 if n is None else n,
+                   max_dist=0.0 if max_dist is None else float(max_dist), include_lines=bool(include_lines))
+
+
+def arcs_to_beziers(commands, args, max_seq_len=None):
+    """``SVGPath.simplify_arcs`` for a batch: every live `a` row (rx, ry, phi in degrees, fA, fS, end; flags read as != 0,
+    radii as absolute values) is dropped when both radii are 0 or when its start and end are close (the test of
+    `canonicalize`, step 2), and otherwise becomes max(floor(|sweep| / 45 deg), 1) `c` rows over equal parts of its sweep: the
+    centre parametrisation and the control points of ``SVGCommandArc.to_beziers``, formula by formula, in float64.  Every other
+    row passes through.  Shapes, framing, the returned dict (without "lengths") and the invalid cases are those of `split`,
+    except that no icon is invalid for holding an arc.  Two deliberate deviations from the reference:
+      1. radii too small for the chord (x'^2 / rx^2 + y'^2 / ry^2 = lambda > 1): both radii are scaled by sqrt(lambda), as the
+         SVG implementation note F.6.6 asks; the chord is then a diameter and the sweep half a turn (4 rows).  The reference
+         keeps the radii, its curve then misses the start point, and its sweep rests on the sign of a determinant that is
+         zero up to rounding.
+      2. exactly one radius 0: one `l` to the end position (note F.6.2).  The reference divides by zero and raises.
+    A dropped arc leaves no row: the command behind it starts where the row before the arc ended, as everywhere in this
+    layout (the reference's command objects keep their own start points, and it writes an `m` right before a dropped arc
+    from the start point of the command that follows)."""
+    return _expand("arcs_to_beziers", commands, args, max_seq_len, arcs=True)
 
 
 def numericalize(args, commands, n=256):

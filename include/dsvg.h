@@ -53,7 +53,9 @@ extern "C" {
  * 18: the one-launch attention input gradient of version 7 removed: its entry point, its workspace query and its debug clock
  *     (opt-in since round 6, never ahead of the two launches it replaced); a layer of dsvg_attn_pack_bwd is back to 128
  *     fragments (out_proj.weight^T only).
- * 19: dsvg_canonicalize added (the canonical path order of SVG.canonicalize for a whole batch). */
+ * 19: dsvg_canonicalize added (the canonical path order of SVG.canonicalize for a whole batch).
+ *     Still 19: dsvg_paths_expand added (split and arc conversion for a whole batch).  No exported signature changed, and a
+ *     library built without it fails to load by the missing symbol; tests/test_paths_host.py pins 19 for the binding. */
 #define DSVG_ABI_VERSION 19
 
 const char* dsvg_last_error(void);
@@ -707,6 +709,59 @@ int dsvg_canonicalize(int32_t itype, const void* commands, const void* args, int
                       int32_t S_out, int32_t layout, int32_t numericalize, void* out_commands, void* out_args,
                       int32_t* n_groups, int32_t* len_groups, int32_t* source_group, uint8_t* reversed, uint8_t* valid,
                       void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Commands split and arcs converted, for a whole batch (csrc/paths_expand.hip): SVGPath.split (deepsvg/svglib/svg_path.py:
+ * 615-630 with SVGCommandLine.split / SVGCommandBezier.split / .length, svg_command.py:255-270, 369-413) and
+ * SVGPath.simplify_arcs (svg_path.py:280-293 with SVGCommandArc.to_beziers, svg_command.py:458-511) on the tensors themselves.
+ * Every input row becomes 0..k output rows: a count per row, a prefix sum, a gather.  The definition
+ * (tests/paths_expand_ref.py restates it in float64):
+ *  rows: commands [N, G, S] / args [N, G, S, 11] fp32, G * S <= 2048.  Row 0 of a group is its frame (SOS) and is never read
+ *    as a command; a group ends at its first EOS (a group whose row 0 is EOS is empty), rows at or behind it are dead and
+ *    never read.  The start point of a row is the end position (args 9:11) of the row before it, whatever that row holds.  A
+ *    live row that is not expanded (`m`, `z`, a SOS behind row 0, an `l` when include_lines = 0, every `l` / `c` in arc mode)
+ *    passes through as one row.  A command outside 0..6 on a live row makes the icon invalid.
+ *  arithmetic: float64, one IEEE operation at a time (no fused multiply-add), each written value rounded to fp32 once.  With
+ *    lerp(a, b, t) = (1 - t) a + t b.  The last piece of an expanded row carries the input row's end position bit for bit;
+ *    as the layout stores no start points, consecutive pieces join exactly.
+ *  mode DSVG_EXPAND_SPLIT: the length of an `l` is sqrt(dx dx + dy dy) from its start to its end; of a `c` the sum, i = 1..99
+ *    in order, of the distances between the points at z = (i - 1) / 99 and i / 99, a point being ((b0 p0 + b1 p1) + b2 p2) +
+ *    b3 p3 with w = 1 - z, b0 = (w w) w, b1 = (3 (w w)) z, b2 = (3 w) (z z), b3 = (z z) z (the Bernstein form in float64: not
+ *    the fp32 power basis of csrc/svg_seq.h, which is what sample_points draws).  k = n when n > 0, else max(ceil(length /
+ *    max_dist), 1).  An `l` becomes k `l` rows with ends lerp(p0, p1, (i + 1) / k); a `c` becomes k `c` rows, row i holding
+ *    the sub-curve on [a, b] = [i / k, (i + 1) / k] by its blossom: control1 = B(a, a, b), control2 = B(a, b, b), end =
+ *    B(b, b, b), where B(u, v, w) runs de Casteljau's three lerp levels with u, then v, then w.  A row with k = 1 is copied.
+ *    A live `a` makes the icon invalid (the reference raises).  lengths fp32 [N, G, S]: the length of every live `l` / `c`,
+ *    0 elsewhere.
+ *  mode DSVG_EXPAND_ARCS: a live `a` holds rx, ry (read as absolute values), phi in degrees, fA, fS (read as != 0) and its end.
+ *    It is dropped when both radii are 0 or when start and end are close (|s - e| <= 1e-8 + 1e-5 |e| in both coordinates);
+ *    with exactly one radius 0 it becomes one `l` to its end (SVG implementation note F.6.2; the reference divides by zero).
+ *    Otherwise, formula by formula as SVGCommandArc._get_center_parametrization: h = (p1 - p2) / 2, m = (p1 + p2) / 2, (x', y')
+ *    = h rotated by -phi, lambda = x'^2 / rx^2 + y'^2 / ry^2; when lambda > 1 both radii are multiplied by sqrt(lambda) and
+ *    the centre coefficient is 0 (note F.6.6; the reference keeps the radii, and its sweep then rests on the sign of a
+ *    rounded zero), else coefficient = sqrt(max((rx^2 ry^2 - rx^2 y'^2 - ry^2 x'^2) / (rx^2 y'^2 + ry^2 x'^2), 0)), negated
+ *    when fA == fS; c' = coefficient (rx y' / ry, -ry x' / rx), centre = c' rotated by phi + m, d = (p' - c') / r, e = -(p' +
+ *    c') / r, theta1 = the signed angle from (1, 0) to d, sweep = the signed angle from d to e in degrees (acos of the clipped
+ *    dot product of the normalised vectors, negative when the determinant is < 0), plus 360 when negative, minus 360 when fS
+ *    = 0 and it is > 0; when lambda > 1 the chord is a diameter and the sweep is 180 (fS) or -180.  The row becomes k = max(floor(|sweep| / 45), 1) `c` rows over equal parts of the sweep, eta_i =
+ *    theta1 + (1 / k) (i sweep) in degrees; with t1, t2 the radians of a part, alpha = sin(t2 - t1) (sqrt(4 + 3 tan^2((t2 -
+ *    t1) / 2)) - 1) / 3, P(t) = centre + (rx cos t, ry sin t) rotated by phi, P'(t) = (-rx sin t, ry cos t) rotated by phi:
+ *    control1 = P(t1) + alpha P'(t1), control2 = P(t2) - alpha P'(t2), end = P(t2).
+ *  validity: a live `l`, `c` or `a` whose start point, arguments in use, or computed length / sweep is not finite makes the
+ *    icon invalid (no NaN is converted to a count; counts are clamped to S_out before the sum), and so does a group that
+ *    needs more than S_out - 2 rows.  An invalid icon is written as SOS, EOS... in every group, len_groups 0, source_row -1.
+ *  out_commands [N, G, S_out] / out_args [N, G, S_out, 11] fp32, G * S_out <= 2048: SOS, the rows, EOS to the end; every slot
+ *    CMD_ARGS_MASK does not enable for the row's command is -1.  len_groups int32 [N, G]: rows between SOS and the first EOS.
+ *    source_row int32 [N, G, S_out]: the input row (index in its group) an output row came from, -1 on SOS, EOS, padding.
+ *    lengths: NULL in arc mode.  valid uint8 [N].
+ *  One workgroup per icon: a ballot scan for the EOS rule, one lane per live row for its count, a prefix sum over the counts
+ *    (each group's base subtracted), and every output row finds its input row by binary search in the prefix and computes its
+ *    own piece.  No atomics, no workspace, no device-to-host read: bit-reproducible, capturable. */
+#define DSVG_EXPAND_SPLIT 0
+#define DSVG_EXPAND_ARCS 1
+int dsvg_paths_expand(int32_t mode, const float* commands, const float* args, int64_t N, int32_t G, int32_t S, int32_t S_out,
+                      int32_t n, double max_dist, int32_t include_lines, float* out_commands, float* out_args,
+                      int32_t* len_groups, int32_t* source_row, float* lengths, uint8_t* valid, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The argument head fused with its consumers (csrc/head_fused.hip): args_fcn = Linear(256 -> n_args *
