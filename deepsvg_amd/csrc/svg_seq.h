@@ -1,6 +1,7 @@
 // Sequences of drawing commands on the device, stated once for csrc/metrics.hip (sample_points and its backward),
 // csrc/raster.hip (the chords of an image and their backward), csrc/paths.hip (canonical path order),
-// csrc/paths_expand.hip (commands split, arcs converted) and csrc/assemble.hip (batch assembly): the command vocabulary
+// csrc/paths_expand.hip (commands split, arcs converted), csrc/paths_simplify.hip (Beziers fitted) and csrc/assemble.hip
+// (batch assembly): the command vocabulary
 // and the argument columns of SVGTensor (deepsvg/difflib/tensor.py:8-41), the ballot prefix scan that gives every drawing
 // command its output offset and the scans built on it, the prefix sum of counts for rows that become several, the count
 // clamp of a cloud, and the curve a drawing command draws with its transpose.
@@ -62,8 +63,8 @@ __device__ __forceinline__ void block_flag_scan(int n, C* __restrict__ pre, int*
 }
 
 // Exclusive prefix SUM of a non-negative count by one workgroup of SP_THREADS threads, for the kernels where an item becomes
-// 0..k output rows (csrc/paths_expand.hip): an inclusive shuffle scan per wave and chunk, then the prefix over the wave totals
-// as above.  pre[t] = sum of count(i) over items i < t, for t in 0..n (pre[n] = the total); the caller keeps n times the
+// 0..k output rows (csrc/paths_expand.hip, csrc/paths_simplify.hip): an inclusive shuffle scan per wave and chunk, then the
+// prefix over the wave totals as above.  pre[t] = sum of count(i) over items i < t, for t in 0..n (pre[n] = the total); the caller keeps n times the
 // largest count below 2^31.  count(t) is called by every thread for t < the chunk-rounded n and must return 0 past n.
 template <int MAXT, typename F>
 __device__ __forceinline__ void block_count_sum(int n, int* __restrict__ pre, int* __restrict__ wtot, F count) {

@@ -175,6 +175,9 @@ SIGNATURES = {
     "dsvg_raster_segments_bwd": (c_i32, [vp, vp, vp, c_i64, c_i32, c_i32, c_i32, c_i32, vp, vp]),
     "dsvg_canonicalize": (c_i32, [c_i32, vp, vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dsvg_paths_expand": (c_i32, [c_i32, vp, vp, c_i64, c_i32, c_i32, c_i32, c_i32, C.c_double, c_i32, vp, vp, vp, vp, vp, vp, vp]),
+    "dsvg_paths_simplify_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
+    "dsvg_paths_simplify": (c_i32, [vp, vp, c_i64, c_i32, c_i32, c_i32, C.c_double, C.c_double, C.c_double, c_i32, C.c_double, vp,
+                                    c_i64, vp, vp, vp, vp, vp, vp]),
     "dsvg_ffn_pack_bytes": (c_i64, [c_i32, c_i32]),
     "dsvg_ffn_pack": (c_i32, [vp, vp, c_i32, c_i32, c_i32, vp, vp, vp, vp, vp]),
     "dsvg_ffn_fwd": (c_i32, [vp, vp, vp, vp, vp, vp, vp, vp, c_i64, c_f32, c_f32, c_u32, c_u32, vp, c_i32, vp]),

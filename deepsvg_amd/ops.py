@@ -1492,6 +1492,33 @@ def paths_expand(commands, args, s_out, arcs=False, n=0, max_dist=0.0, include_l
     return res
 
 
+def paths_simplify(commands, args, s_out, tolerance, epsilon, cos_threshold, force_smooth, unit):
+    """commands [N, G, S] / args [N, G, S, 11] float32, G * S <= 2048 and G * s_out <= 2048 -> the dict of
+    deepsvg_amd.paths.simplify: "commands" [N, G, s_out], "args" [N, G, s_out, 11] float32, "len_groups" int32 [N, G],
+    "source_row" int32 [N, G, s_out], "valid" bool [N].  cos_threshold = cos(angle_threshold), in float64.  One launch and a
+    workspace of dsvg_paths_simplify_workspace_bytes; include/dsvg.h has the definition"""
+    _chk(commands, args)
+    assert commands.dim() == 3 and args.dim() == 4 and args.shape[:3] == commands.shape and args.shape[3] == N_ARGS
+    assert commands.dtype == args.dtype == torch.float32 and commands.is_contiguous() and args.is_contiguous()
+    N, G, S = commands.shape
+    dev = commands.device
+    s_out = int(s_out)
+    L = _l.load()
+    out_c = torch.empty(N, G, s_out, dtype=torch.float32, device=dev)
+    out_a = torch.empty(N, G, s_out, N_ARGS, dtype=torch.float32, device=dev)
+    len_groups = torch.empty(N, G, dtype=torch.int32, device=dev)
+    source_row = torch.empty(N, G, s_out, dtype=torch.int32, device=dev)
+    valid = torch.empty(N, dtype=torch.bool, device=dev)
+    ws_bytes = L.dsvg_paths_simplify_workspace_bytes(N, G, S)          # the rows a job emitted, until they are compacted
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=dev)
+    _l.check(L.dsvg_paths_simplify(commands.data_ptr(), args.data_ptr(), N, G, S, s_out, float(tolerance), float(epsilon),
+                                   float(cos_threshold), int(bool(force_smooth)), float(unit), ws.data_ptr(), ws_bytes,
+                                   out_c.data_ptr(), out_a.data_ptr(), len_groups.data_ptr(), source_row.data_ptr(),
+                                   valid.data_ptr(), _stream()),
+             "dsvg_paths_simplify")
+    return {"commands": out_c, "args": out_a, "len_groups": len_groups, "source_row": source_row, "valid": valid}
+
+
 # ------------------------------------------------------------------------------------------------
 # device-side batch assembly (svgtensor_dataset.py:164-205)
 # ------------------------------------------------------------------------------------------------

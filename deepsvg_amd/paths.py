@@ -35,9 +35,14 @@ The op is not idempotent in general (steps 4 and 5).  Arcs are out of scope, as 
 `split` and `arcs_to_beziers` are the two steps of the reference's preprocessing chain in which a command becomes several
 (``SVGPath.split``, svglib/svg_path.py:615-630, first and last step of ``simplify_heuristic``; ``SVGPath.simplify_arcs``,
 svg_path.py:280-293): one launch of csrc/paths_expand.hip for the whole batch.  include/dsvg.h has their definition,
-tests/paths_expand_ref.py restates it in float64.  The chain back into the model is
-``arcs_to_beziers -> split(max_dist=7.5 * 256 / 24) -> canonicalize(numericalize=256)``; only the Bezier fit between the
-reference's two splits (``SVGPath.simplify``) stays on the host.
+tests/paths_expand_ref.py restates it in float64.
+
+`simplify` is the Bezier fit between the reference's two splits (``SVGPath.simplify``, svg_path.py:391-613: Schneider's curve
+fit with Newton reparametrisation on the smooth stretches of a path, Ramer-Douglas-Peucker on the rest): one launch of
+csrc/paths_simplify.hip for the whole batch; include/dsvg.h has its definition, tests/paths_simplify_ref.py restates it in
+float64.  `simplify_heuristic` is ``SVGPath.simplify_heuristic`` (svg_path.py:386-389) as three launches.  The chain back into
+the model, as every data set was preprocessed, is
+``arcs_to_beziers -> simplify_heuristic -> canonicalize(numericalize=256)``, all of it on the device.
 """
 import math
 
@@ -46,7 +51,7 @@ import torch
 from . import ops
 from .svgtensor import CMD_ARGS_MASK, C_ID
 
-__all__ = ["canonicalize", "numericalize", "split", "arcs_to_beziers"]
+__all__ = ["canonicalize", "numericalize", "split", "arcs_to_beziers", "simplify", "simplify_heuristic"]
 
 MAX_ROWS = 2048      # G * S rows per icon: the largest icon the model accepts in a two-stage config, 8 groups of 256
 
@@ -98,7 +103,7 @@ def canonicalize(commands, args, max_num_groups=None, max_seq_len=None, layout="
 
 
 def _expand(name, commands, args, max_seq_len, **mode):
-    """the argument checks and the launch `split` and `arcs_to_beziers` share"""
+    """the argument checks and the launch `split`, `arcs_to_beziers` and `simplify` share"""
     if commands.dim() not in (2, 3) or args.dim() != commands.dim() + 1 or args.shape[:-1] != commands.shape \
             or args.shape[-1] != 11:
         raise ValueError(f"{name}: commands (N, G, S) with args (N, G, S, 11), or (N, S) with (N, S, 11); got "
@@ -115,7 +120,8 @@ def _expand(name, commands, args, max_seq_len, **mode):
     if S < 2 or G * S > MAX_ROWS or G * s_out > MAX_ROWS:
         raise ValueError(f"{name}: {G} x {S} rows per icon in, {G} x {s_out} out; at least 2 per group and at most {MAX_ROWS} "
                          f"per icon")
-    res = ops.paths_expand(commands.detach().float().contiguous(), args.detach().float().contiguous(), s_out, **mode)
+    commands, args = commands.detach().float().contiguous(), args.detach().float().contiguous()
+    res = (ops.paths_simplify if name == "simplify" else ops.paths_expand)(commands, args, s_out, **mode)
     if squeeze:
         res = {k: (v if k == "valid" else v.squeeze(1)) for k, v in res.items()}
     return res
@@ -167,6 +173,72 @@ def arcs_to_beziers(commands, args, max_seq_len=None):
     layout (the reference's command objects keep their own start points, and it writes an `m` right before a dropped arc
     from the start point of the command that follows)."""
     return _expand("arcs_to_beziers", commands, args, max_seq_len, arcs=True)
+
+
+def _positive(name, what, v):
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v <= 0:
+        raise ValueError(f"{name}: {what} is finite and > 0; got {v!r}")
+    return float(v)
+
+
+def simplify(commands, args, tolerance=0.1, epsilon=0.1, angle_threshold=179.0, force_smooth=False, unit=256 / 24,
+             max_seq_len=None):
+    """``SVGPath.simplify`` for a batch: in every sub-path (a maximal run of `l` / `c` rows; `m` and `z` pass through) the
+    stretches of `c` rows that join at most 180 - angle_threshold degrees off straight are replaced by cubics fitted
+    through their end points (Schneider's fit: at most 5 rounds of least squares and one Newton step per point, split at the
+    worst point when the squared distance stays >= tolerance), the `l` rows between them by Ramer-Douglas-Peucker lines
+    (a point further than epsilon from the chord is kept).  force_smooth=True fits one curve sequence through a whole
+    sub-path, corners and lines included.  Only end points are read: run `split(max_dist=..., include_lines=False)` first,
+    as `simplify_heuristic` does, to give the fit points along the curves.
+    tolerance and epsilon are in the reference's units (its 24 box): coordinates are divided by `unit` in float64 when they
+    are loaded, the fit runs in reference units, and computed control points are multiplied by `unit` once before the one
+    rounding to float32 (the reference's max(error, error^2) and its comparison of a squared distance with tolerance are not
+    scale-invariant).  Shapes, framing, dtype handling and detaching are those of `split`.  -> a dict, float32, no gradient:
+      "commands" (N, G, S_out), "args" (N, G, S_out, 11), S_out = max_seq_len + 2 (default S): SOS, the rows, EOS to the end,
+        -1 in every slot CMD_ARGS_MASK does not enable.  Between two segments, and before / behind a segment at the ends of a
+        sub-path, the reference emits a zero-length `l` (its data sets hold them; `canonicalize` step 2 drops them), so a
+        group can grow: at most rows in + segments + 1 rows.
+      "len_groups" int32 (N, G); "source_row" int32 (N, G, S_out): for an `m` / `z` the input row itself, for a written `l` /
+        `c` the input row whose end position the output row carries bit for bit (end positions are copies, never
+        recomputed), -1 on SOS, EOS and padding; "valid" bool (N,).
+    An icon is invalid, and comes back as `split` hands one back, for the reasons `split` has (a live `a`, a command outside
+    the vocabulary, a live value that is not finite), when a group needs more than S_out - 2 rows, and when a fit needs the
+    direction between two points at distance exactly 0 (the reference raises ZeroDivisionError in ``normalize``)."""
+    tolerance, epsilon = _positive("simplify", "tolerance", tolerance), _positive("simplify", "epsilon", epsilon)
+    unit = _positive("simplify", "unit", unit)
+    if isinstance(angle_threshold, bool) or not isinstance(angle_threshold, (int, float)) or not math.isfinite(angle_threshold) \
+            or not 0 <= angle_threshold <= 180:
+        raise ValueError(f"simplify: angle_threshold is finite and within [0, 180]; got {angle_threshold!r}")
+    return _expand("simplify", commands, args, max_seq_len, tolerance=tolerance, epsilon=epsilon,
+                   cos_threshold=math.cos(math.radians(float(angle_threshold))), force_smooth=bool(force_smooth), unit=unit)
+
+
+def simplify_heuristic(commands, args, unit=256 / 24, max_seq_len=None, work_seq_len=None):
+    """``SVGPath.simplify_heuristic`` for a batch, three launches: `split(max_dist=2 * unit, include_lines=False)` into
+    work_seq_len rows per group (default 2048 // G - 2), `simplify(0.1, 0.2, 150.0, unit=unit)` into the same size, and
+    `split(max_dist=7.5 * unit)` into max_seq_len (default S - 2).  Input as for `split`.  -> a dict: "commands", "args",
+    "len_groups" of the last step, and "valid" bool (N,), the AND of the three steps; an icon invalid at any step comes back
+    as `split` hands back an invalid icon."""
+    unit = _positive("simplify_heuristic", "unit", unit)
+    if commands.dim() not in (2, 3):
+        raise ValueError(f"simplify_heuristic: commands (N, G, S) or (N, S); got {tuple(commands.shape)}")
+    G, S = (1 if commands.dim() == 2 else commands.shape[1]), commands.shape[-1]
+    if G < 1 or G > MAX_ROWS // 2:
+        raise ValueError(f"simplify_heuristic: {G} groups, at most {MAX_ROWS // 2}")
+    work = MAX_ROWS // G - 2 if work_seq_len is None else work_seq_len
+    out_len = S - 2 if max_seq_len is None else max_seq_len
+    for what, v in (("work_seq_len", work), ("max_seq_len", out_len)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0 or G * (v + 2) > MAX_ROWS:
+            raise ValueError(f"simplify_heuristic: {what} is an int >= 0 with {G} x ({what} + 2) <= {MAX_ROWS}; got {v!r}")
+    try:
+        first = split(commands, args, max_dist=2 * unit, include_lines=False, max_seq_len=work)
+    except ValueError as e:
+        raise ValueError(str(e).replace("split:", "simplify_heuristic:", 1)) from None
+    fit = simplify(first["commands"], first["args"], 0.1, 0.2, 150.0, unit=unit, max_seq_len=work)
+    last = split(fit["commands"], fit["args"], max_dist=7.5 * unit, max_seq_len=out_len)
+    # an icon invalid at one step is handed on as empty groups, which the later steps pass through: nothing to blank here
+    return {"commands": last["commands"], "args": last["args"], "len_groups": last["len_groups"],
+            "valid": first["valid"] & fit["valid"] & last["valid"]}
 
 
 def numericalize(args, commands, n=256):

@@ -55,7 +55,9 @@ extern "C" {
  *     fragments (out_proj.weight^T only).
  * 19: dsvg_canonicalize added (the canonical path order of SVG.canonicalize for a whole batch).
  *     Still 19: dsvg_paths_expand added (split and arc conversion for a whole batch).  No exported signature changed, and a
- *     library built without it fails to load by the missing symbol; tests/test_paths_host.py pins 19 for the binding. */
+ *     library built without it fails to load by the missing symbol; tests/test_paths_host.py pins 19 for the binding.
+ *     Still 19: dsvg_paths_simplify (+ dsvg_paths_simplify_workspace_bytes) added (the Bezier fit of SVGPath.simplify for a
+ *     whole batch), on the same terms. */
 #define DSVG_ABI_VERSION 19
 
 const char* dsvg_last_error(void);
@@ -762,6 +764,73 @@ int dsvg_canonicalize(int32_t itype, const void* commands, const void* args, int
 int dsvg_paths_expand(int32_t mode, const float* commands, const float* args, int64_t N, int32_t G, int32_t S, int32_t S_out,
                       int32_t n, double max_dist, int32_t include_lines, float* out_commands, float* out_args,
                       int32_t* len_groups, int32_t* source_row, float* lengths, uint8_t* valid, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Beziers fitted through the points of every sub-path, for a whole batch (csrc/paths_simplify.hip): SVGPath.simplify
+ * (deepsvg/svglib/svg_path.py:391-613), the middle step of simplify_heuristic, on the tensors themselves.  The definition
+ * (tests/paths_simplify_ref.py restates it in float64):
+ *  1. rows and sub-paths: commands [N, G, S] / args [N, G, S, 11] fp32, G * S <= 2048, read by the EOS rule of
+ *     dsvg_paths_expand (row 0 is the frame, a group ends at its first EOS).  A sub-path ("run") is a maximal run of live `l`
+ *     / `c` rows; `m`, `z` and a SOS behind row 0 pass through in place and delimit runs.  The points of a run are the start
+ *     of its first row (the end position of the row before it, whatever that row holds) and the end of every row.  Point k of
+ *     an icon is the end position of its row k, read as fp32 and divided by `unit` in float64 at every use: the fit runs in
+ *     the reference's units (its 24 box), because max(error, error^2) and the comparison of a squared distance with
+ *     `tolerance` are not scale-invariant.
+ *  2. segments (subdivide_indices): an `l` closes the open segment.  Between consecutive `c` rows, t1 = 3 (end - control2)
+ *     of the first and t2 = -(3 (control1 - start)) of the second (every coordinate divided by unit first); the segment breaks
+ *     when either norm is <= 1e-8 or when clip((t1x / |t1|) (t2x / |t2|) + (t1y / |t1|) (t2y / |t2|), -1, 1) > cos_threshold
+ *     = cos(angle_threshold), computed by the caller in float64: no acos runs on the device.
+ *  3. emission order (svg_path.py:593-609): RDP on the gap of `l` rows before the first segment, then per segment fitCubic
+ *     followed by RDP on the gap behind it; a run without a `c` is one RDP.  An empty gap (first == last) emits a zero-length
+ *     `l` as the reference does, so a group can grow: at most rows in + segments + 1 rows.  force_smooth: one fitCubic over
+ *     the whole run, `l` rows included.
+ *  4. formulas, float64, one IEEE operation at a time (no fused multiply-add), powers as products, |v| = sqrt(dx dx + dy dy):
+ *     RDP(first, last): dist_i of the interior points i to the line: when the two ends are close (|a - b| <= 1e-8 + 1e-5 |b|
+ *       in both coordinates) |P_i - P_first|, else |dx (ay - py) - dy (ax - px)| / |(dx, dy)| with (dx, dy) = P_last -
+ *       P_first.  The largest, the largest index among equals (a NaN never counts); when it is > epsilon split there, left
+ *       part first, else one `l` to P_last.
+ *     fitCubic(first, last) with tangents t1, t2 (point 6): one interval: control1 = P_first + d t1, control2 = P_last + d t2,
+ *       d = |P_first - P_last| / 3.  Else u_i = (L[first + i] - L[first]) / (L[last] - L[first]) (point 5a), limit =
+ *       max(tolerance, tolerance^2), ordered = true, and at most 5 times: curve = generateBezier; (err, split) =
+ *       computeMaxError; accept the curve when err < tolerance and ordered; stop when err >= limit; ordered = reparametrize;
+ *       limit = err.  Not accepted: split at `split`, left part first.
+ *     generateBezier: per point t = 1 - u, b = (3 u) t, b0 = (t t) t, b1 = b t, b2 = b u, b3 = (u u) u, a1 = t1 b1, a2 = t2 b2,
+ *       tmp = (P_i - P_first (b0 + b1)) - P_last (b2 + b3); C00 = sum a1.a1, C01 = sum a1.a2, C11 = sum a2.a2, X0 = sum
+ *       a1.tmp, X1 = sum a2.tmp (point 5b; a.b = ax bx + ay by).  det = C00 C11 - C01 C01; when |det| > 1e-12: alpha1 = (X0 C11
+ *       - X1 C01) / det, alpha2 = (C00 X1 - C01 X0) / det; else with c0 = C00 + C01, c1 = C01 + C11 both are X0 / c0 when |c0|
+ *       > 1e-12, else X1 / c1 when |c1| > 1e-12, else 0.  seg = |P_last - P_first|; when alpha1 or alpha2 < 1e-12 seg both
+ *       become seg / 3; else when (t1 alpha1).line - (t2 alpha2).line > seg seg, line = P_last - P_first, too.  control1 =
+ *       P_first + t1 alpha1, control2 = P_last + t2 alpha2.
+ *     the curve at t: ((b0 p0 + b1 c1) + b2 c2) + b3 p3 with w = 1 - t, b0 = (w w) w, b1 = (3 (w w)) t, b2 = (3 w) (t t), b3 =
+ *       (t t) t; its derivatives ((3 (w w)) (c1 - p0) + ((6 w) t) (c2 - c1)) + (3 (t t)) (p3 - c2) and (6 w) ((c2 - 2 c1) + p0)
+ *       + (6 t) ((p3 - 2 c2) + c1).
+ *     computeMaxError: over the interior points d = |curve(u_i) - P_i|, err_i = d d; the largest, the largest index among
+ *       equals.  The accept test compares this SQUARED distance with tolerance, as the reference does.
+ *     reparametrize: for every point, the ends included, f = curve(u) - P, num = f.curve'(u), den = curve'(u).curve'(u) +
+ *       f.curve''(u); u stays when -1.12e-16 <= den <= 1.12e-16, else u - num / den.  ordered = no u_i <= u_(i-1).
+ *  5. stated summation order: (a) chord lengths are accumulated once per run in ascending order into the table L, L = 0 at
+ *     the run's first point; (b) each of the five sums is 64 strided partials - partial j adds the terms of i = j, j + 64,
+ *     ... in ascending order, starting from 0.0 - combined by partial[j] += partial[j + d] for j < d, d = 32, 16, ..., 1.
+ *  6. tangents are never stored: at the first point of a job (a top-level fitCubic) t1 = normalize(P[first + 1] - P[first]),
+ *     at its last point t2 = normalize(P[last - 1] - P[last]); at a split index s the left part ends with c = normalize(P[s -
+ *     1] - P[s + 1]) and the right part starts with -c.  normalize(v) = (vx / |v|, vy / |v|).
+ *  validity: the cases of dsvg_paths_expand in split mode (a live `a`, a command outside 0..6, a live `l` / `c` whose start
+ *     point or arguments in use are not finite), a group that needs more than S_out - 2 rows, a direction between two points
+ *     at distance exactly 0 (the reference raises ZeroDivisionError in normalize), L[last] == L[first] in a fit, and a fit
+ *     whose distances are all NaN.  An invalid icon is written as SOS, EOS... in every group, len_groups 0, source_row -1.
+ *  out_commands [N, G, S_out] / out_args [N, G, S_out, 11] fp32, G * S_out <= 2048: SOS, the rows, EOS to the end; -1 in every
+ *     slot CMD_ARGS_MASK does not enable.  Control points are multiplied by unit once, then rounded to fp32 once; end
+ *     positions are copies of input values.  len_groups int32 [N, G].  source_row int32 [N, G, S_out]: for `m` / `z` the
+ *     input row itself, for a written `l` / `c` the input row whose end position it carries bit for bit, -1 on SOS, EOS and
+ *     padding.  valid uint8 [N].
+ *  workspace: dsvg_paths_simplify_workspace_bytes(N, G, S) = 20 bytes per slot, 2 G S slots per icon, 16-byte aligned: the
+ *     rows a job emitted until they are compacted.  tolerance, epsilon, unit finite and > 0; cos_threshold in [-1, 1].
+ *  One workgroup per icon; csrc/paths_simplify.hip has the phases.  No atomics, no device-to-host read: bit-reproducible. */
+int64_t dsvg_paths_simplify_workspace_bytes(int64_t N, int32_t G, int32_t S);
+int dsvg_paths_simplify(const float* commands, const float* args, int64_t N, int32_t G, int32_t S, int32_t S_out,
+                        double tolerance, double epsilon, double cos_threshold, int32_t force_smooth, double unit,
+                        void* workspace, int64_t workspace_bytes, float* out_commands, float* out_args, int32_t* len_groups,
+                        int32_t* source_row, uint8_t* valid, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The argument head fused with its consumers (csrc/head_fused.hip): args_fcn = Linear(256 -> n_args *
