@@ -320,6 +320,9 @@ def gemm(a, b, *, a_kc=True, b_kc=True, bias=None, res=None, res_pre=False, act=
          accumulate=False, split_k=1, impl=0, rowsum=None):
     """C[M,N] = epi(sum_k A(m,k) B(n,k)).  a: [M,K] if a_kc else [K,M]; b: [N,K] if b_kc else [K,N].
     rowsum (fp32 [M], only with split_k > 1): also rowsum[m] = sum_k A(m,k) (bias gradient of a weight-grad GEMM).
+    a, b, out may be views of larger row-major buffers: rows behind the view and the columns between its width and its row
+    stride are never read into a result (NaN there is harmless) and never written; without accumulate the old contents of
+    out / rowsum are not read either.
     The descriptor of a call signature (shapes, strides, options - everything but the pointers) is validated and
     built once and re-used: the Python dispatch of the ~250 GEMMs of a train step is otherwise as long as the step."""
     _chk(a, b, bias, res, gate, seed, out)
@@ -500,7 +503,11 @@ def attention_fwd(qkv, key_mask, n_seq, S, n_heads, scale, drop_p=0.0, drop_site
     """seq_off (int32 [n_seq+1], device): packed layout, sequence b = rows seq_off[b]..seq_off[b+1]-1 (<= S rows, all
     keys visible, key_mask must be None); rows past seq_off[n_seq] are zero-filled.
     causal: query i attends keys j <= i (autoregressive decoder; dense layout only).
-    path_stage: a path-level stage of a two-stage config (S > 64, bf16: the matrix-core long kernels)."""
+    path_stage: a path-level stage of a two-stage config (S > 64, bf16: the matrix-core long kernels).
+    What is ignored (tests/test_ignored_inputs_gpu.py): the q|k|v rows past seq_off[n_seq] may hold anything, NaN included;
+    the K / V rows of masked keys and the rows of the other sequences of a tile may hold any FINITE values (a masked
+    probability is an exact 0, and 0 * finite is 0 in the matrix products; NaN there is contagious, as in the reference).
+    attention_bwd returns exact zeros as dk / dv of a masked key and, like attention_fwd, in the rows past the last sequence."""
     _chk(qkv, key_mask, seed, seq_off)
     rows = qkv.shape[0]
     assert qkv.is_contiguous() and qkv.shape[1] == 3 * 32 * n_heads, "attention needs head_dim == 32"
@@ -827,7 +834,8 @@ def gather_groups(src, idx, n_groups, S, out=None, n_src=None):
 
 def pack_tokens(commands, args, key_mask, n_seq, S):
     """packed token layout of the first encoder stage (include/dsvg.h): returns seq_off int32 [n_seq+1] and the packed
-    commands [n_seq*S], args [n_seq*S, n_args], positions int32 [n_seq*S] (rows past seq_off[-1] replicate token 0)"""
+    commands [n_seq*S], args [n_seq*S, n_args], positions int32 [n_seq*S] (rows past seq_off[-1] replicate token 0).
+    Only the tokens key_mask names (and token 0) are read: what follows a sequence's end does not matter."""
     _chk(commands, args, key_mask)
     assert commands.dtype == torch.float32 and args.dtype == torch.float32 and commands.is_contiguous() and \
         args.is_contiguous() and commands.numel() == n_seq * S
@@ -1761,7 +1769,10 @@ def attn_block_fwd(x, packed_layer, in_bias, out_bias, gamma, beta, key_mask, n_
                    into=None):
     """x1 = x + drop_r(out_proj(MHA(LayerNorm(x)))) [+ drop(seq_add[sequence])]  (x bf16 [rows, 256], 8 heads, S <= 32)
     in one launch.  seq_add (bf16 [n_seq, 256], dense layouts): the decoder's per-sequence conditioning term.
-    train=False -> x1;  train=True -> (x1, xn, qkv, ao, mean, rstd): what the unfused backward reads."""
+    train=False -> x1;  train=True -> (x1, xn, qkv, ao, mean, rstd): what the unfused backward reads.
+    Rows behind the last sequence (bucket padding up to `rows`) are computed from themselves alone, in tiles of 32 that attend
+    to themselves only: they are finite where x is, they are NOT cleared (unlike attention_fwd's), and nothing they hold -
+    NaN included - reaches a row of a sequence.  Inside a tile a sequence sees its own rows only."""
     _chk(x, packed_layer, in_bias, out_bias, gamma, beta, key_mask, seed, seq_off, tiles)
     rows = x.shape[0]
     assert x.dtype == torch.bfloat16 and x.is_contiguous() and x.shape[1] == 256
@@ -1880,7 +1891,9 @@ def gs_layer_bwd(dx2, packed_bwd_layer, x, mean1, rstd1, qkv, x1, mean2, rstd2, 
     want_dx1: test hook; the step passes False.  In the kernel it is one guarded store; the tests check dx1 itself and use it
     as the comparator of dg at drop_p > 0, where dx1 cannot be recovered from dx1m.
     want_dg: one more result at the end, dg [n_seq, 256] = bcast_add_bwd(dx1, n_seq, S, drop_p, site0 + 2, seed) bit for bit
-    (the per-sequence term's gradient, formed in the same launch)."""
+    (the per-sequence term's gradient, formed in the same launch).
+    dgamma2 / dbeta2 / dgamma1 / dbeta1, when given, are overwritten: what they held is not read.  K and V of the saved
+    q|k|v at masked keys may hold any finite values; dk / dv there come back as exact zeros."""
     _chk(dx2, packed_bwd_layer, x, mean1, rstd1, qkv, x1, mean2, rstd2, h, gamma1, gamma2, key_mask, seed)
     rows = n_seq * S
     assert dx2.dtype == torch.bfloat16 and dx2.is_contiguous() and tuple(dx2.shape) == (rows, 256) and 32 % S == 0
