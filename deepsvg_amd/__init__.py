@@ -7,7 +7,10 @@ Public surface mirrors the reference (alexandre01/deepsvg):
     deepsvg_amd.metrics         <->  deepsvg.difflib: SVGTensor.sample_points + chamfer_loss (reconstruction error)
                                      and the other losses of difflib/loss.py: svg_emd_loss, svg_length_loss, continuity_loss
     deepsvg_amd.render          <->  deepsvg.svglib: SVG.draw of a decoded batch (stroke / fill coverage images, interpolation)
-    deepsvg_amd.paths           <->  deepsvg.svglib: SVG.canonicalize + numericalize of a batch (the form the encoder was trained on)
+    deepsvg_amd.paths           <->  deepsvg.svglib: SVG.canonicalize + numericalize of a batch (the form the encoder was trained on),
+                                     its preprocessing chain, and SVG.zoom / rotate / translate / normalize
+    deepsvg_amd.dataset         <->  deepsvg.svgtensor_dataset (stored augmentations); deepsvg_amd.svg_dataset <-> deepsvg.svg_dataset
+                                     (augmentation on the fly); both imported by name, as cfg.dataloader_module
 """
 # (No process-wide side effects on import.  The data-parallel hipGraph step wants GPU_MAX_HW_QUEUES=6 in the environment BEFORE
 # the HIP runtime comes up - see trainer.HW_QUEUES_NOTE; bench.py sets it, TrainStep warns when a data-parallel trainer

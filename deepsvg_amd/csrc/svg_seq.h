@@ -1,7 +1,7 @@
 // Sequences of drawing commands on the device, stated once for csrc/metrics.hip (sample_points and its backward),
 // csrc/raster.hip (the chords of an image and their backward), csrc/paths.hip (canonical path order),
-// csrc/paths_expand.hip (commands split, arcs converted), csrc/paths_simplify.hip (Beziers fitted) and csrc/assemble.hip
-// (batch assembly): the command vocabulary
+// csrc/paths_expand.hip (commands split, arcs converted), csrc/paths_simplify.hip (Beziers fitted), csrc/paths_transform.hip
+// (affine step programs) and csrc/assemble.hip (batch assembly): the command vocabulary, the argument mask
 // and the argument columns of SVGTensor (deepsvg/difflib/tensor.py:8-41), the ballot prefix scan that gives every drawing
 // command its output offset and the scans built on it, the prefix sum of counts for rows that become several, the count
 // clamp of a cloud, and the curve a drawing command draws with its transpose.
@@ -20,6 +20,8 @@ namespace {
 constexpr int CMD_M = 0, CMD_L = 1, CMD_C = 2, CMD_A = 3, CMD_EOS = 4, CMD_SOS = 5, CMD_Z = 6, N_CMD = 7;
 constexpr int N_ARGS = 11;                // rx, ry, phi, fA, fS, control1 (x, y), control2 (x, y), end (x, y)
 constexpr int ARG_CONTROL1 = 5, ARG_CONTROL2 = 7, ARG_END = 9;      // column of x; y is the column after it
+// deepsvg/difflib/tensor.py:15-21, bit a of entry c = CMD_ARGS_MASK[c][a]
+__device__ __constant__ uint32_t kCmdArgsMask[N_CMD] = {0x600u, 0x600u, 0x7E0u, 0x61Fu, 0u, 0u, 0u};
 
 constexpr int SP_THREADS = 256;
 constexpr int SP_MAX_TOK = 2048;          // G * L tokens of one cloud / image / icon: 8 chunks of 256

@@ -17,8 +17,11 @@ Same names as the reference where the surface is kept: `SVGTensorDataset(data_di
 max_num_groups, max_seq_len, max_total_len, filter_uni, filter_platform, filter_category, train_ratio, df, PAD_VAL)`
 (svgtensor_dataset.py:18-19), `get`, `get_data`-equivalent keys ("commands", "args", "args_rel", their
 "_grouped" forms, "filling", "label"), `__len__ = len(df) * nb_augmentations` (:111-112), `load_dataset(cfg)`
-(:230-233).  Not carried over: the `svg=` path of `get` and the "tensor" keys (they return drawing objects of the
-reference's svglib, a visualisation path outside the hot path).
+(:230-233).  Not carried over: the "tensor" keys (they return drawing objects of the reference's svglib, a visualisation
+path outside the hot path) and the `svg=` path of `get`, which takes such an object.  What that path is for - icons of the
+user's own, augmented afresh for every batch - is `deepsvg_amd.svg_dataset`: a PackedSVGStore in its float32 form
+(`from_icons(numericalized=False)`, or `from_batch` straight from the device chain of `deepsvg_amd.paths`) and
+`SVGDataset.batch`, which zooms, translates and numericalises the rows while it assembles them.
 """
 import os
 import pickle
@@ -67,9 +70,21 @@ def _as_rows(t):
     return r[:, ROW_COLS].astype(np.int16)
 
 
+def _as_float_rows(t):
+    a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    a = a.reshape(-1, 14)[:, ROW_COLS].astype(np.float32)
+    if a.size and not np.isfinite(a).all():
+        raise DsvgError("PackedSVGStore: a row holds a value that is not finite")
+    if a.size and (not np.array_equal(np.rint(a[:, 0]), a[:, 0]) or a[:, 0].min() < 0 or a[:, 0].max() > 6):
+        raise DsvgError("PackedSVGStore: command index outside 0..6")
+    return a
+
+
 class PackedSVGStore:
     """All icons of a dataset as flat arrays (host numpy or device torch):
-      rows       int16 [R, 12]           (command, 11 arguments) per stored drawing command
+      rows       int16 [R, 12]           (command, 11 arguments) per stored drawing command; or float32 [R, 12], the
+                                         form `deepsvg_amd.svg_dataset` augments and numericalises as it assembles: raw
+                                         coordinates in a view box of size `viewbox` (a float; None for the int16 form)
       slot_off   int32 [n_variants*G+1]  row range of slot variant*G + group
       var_base   int32 [n_icons+1]       variants (stored augmentations, the list entries of the .pkl "tensors",
                                          svgtensor_dataset.py:106-109,156) of icon i are var_base[i] .. var_base[i+1]-1
@@ -77,18 +92,27 @@ class PackedSVGStore:
       label      int64 [n_icons] or None
     """
 
-    def __init__(self, rows, slot_off, var_base, filling, label, G, ids=None, max_group_len=0, max_total_len=0):
+    def __init__(self, rows, slot_off, var_base, filling, label, G, ids=None, max_group_len=0, max_total_len=0,
+                 viewbox=None):
         self.rows, self.slot_off, self.var_base, self.filling, self.label = rows, slot_off, var_base, filling, label
+        self.viewbox = None if viewbox is None else float(viewbox)
+        if self.is_float != (self.viewbox is not None):
+            raise DsvgError("PackedSVGStore: float32 rows come with a view box, int16 rows without one")
         self.G = int(G)
         self.ids = list(ids) if ids is not None else None
         self.max_group_len, self.max_total_len = int(max_group_len), int(max_total_len)
 
     # ---- construction -------------------------------------------------------------------------------------------
     @classmethod
-    def from_icons(cls, icons, fillings=None, labels=None, max_num_groups=8, ids=None):
+    def from_icons(cls, icons, fillings=None, labels=None, max_num_groups=8, ids=None, numericalized=True, viewbox=24.0):
         """icons[i][v] = list of <= max_num_groups group tensors [len, 14] (variant v of icon i);
-        fillings[i] = per-group filling list of icon i (shared by its variants, as in the .pkl files)"""
+        fillings[i] = per-group filling list of icon i (shared by its variants, as in the .pkl files).
+        numericalized=False builds the float32 form: rows as they are (finite values, integer commands), drawn in a view
+        box of size `viewbox` (ignored otherwise)"""
         G = int(max_num_groups)
+        as_rows, dtype = (_as_rows, np.int16) if numericalized else (_as_float_rows, np.float32)
+        if not numericalized and not (isinstance(viewbox, (int, float)) and np.isfinite(viewbox) and viewbox > 0):
+            raise DsvgError(f"PackedSVGStore: viewbox is a finite number > 0; got {viewbox!r}")
         rows, lens, var_base = [], [], [0]
         max_len = max_tot = 0
         for i, variants in enumerate(icons):
@@ -97,7 +121,7 @@ class PackedSVGStore:
             for groups in variants:
                 if len(groups) > G:
                     raise DsvgError(f"PackedSVGStore: icon {i} has {len(groups)} groups > max_num_groups={G}")
-                g_rows = [_as_rows(g) for g in groups]
+                g_rows = [as_rows(g) for g in groups]
                 g_lens = [r.shape[0] for r in g_rows] + [0] * (G - len(g_rows))
                 rows.extend(g_rows)
                 lens.extend(g_lens)
@@ -110,16 +134,44 @@ class PackedSVGStore:
             for i, f in enumerate(fillings):
                 f = list(f)[:G]
                 fill[i, :len(f)] = f
-        rows = np.concatenate(rows + [np.zeros((0, 12), np.int16)], axis=0)
+        rows = np.concatenate(rows + [np.zeros((0, 12), dtype)], axis=0)
         if rows.shape[0] == 0:
-            rows = np.zeros((1, 12), np.int16)      # keep the device array non-empty (never read: every len is 0)
+            rows = np.zeros((1, 12), dtype)         # keep the device array non-empty (never read: every len is 0)
         slot_off = np.zeros(len(lens) + 1, dtype=np.int64)
         np.cumsum(np.asarray(lens, dtype=np.int64), out=slot_off[1:])
         if slot_off[-1] >= 2 ** 31:
             raise DsvgError("PackedSVGStore: more than 2^31 rows")
         label = None if labels is None else np.asarray(labels, dtype=np.int64).reshape(n_icons)
         return cls(np.ascontiguousarray(rows), slot_off.astype(np.int32), np.asarray(var_base, dtype=np.int32), fill,
-                   label, G, ids, max_len, max_tot)
+                   label, G, ids, max_len, max_tot, None if numericalized else viewbox)
+
+    @classmethod
+    def from_batch(cls, commands, args, len_groups, filling=None, labels=None, viewbox=256.0):
+        """The float32 form straight from the padded output of `paths.canonicalize` / `paths.simplify_heuristic`: commands
+        (N, G, S) with args (N, G, S, 11) (a group is SOS, its rows, EOS...) and len_groups (N, G), the rows of each group.
+        Packed where the tensors live, with torch ops; one variant per icon.  filling (N, G) and labels (N,) optional."""
+        if commands.dim() != 3 or args.shape != commands.shape + (11,) or len_groups.shape != commands.shape[:2]:
+            raise DsvgError(f"PackedSVGStore.from_batch: commands (N, G, S), args (N, G, S, 11), len_groups (N, G); got "
+                            f"{tuple(commands.shape)}, {tuple(args.shape)} and {tuple(len_groups.shape)}")
+        if not (isinstance(viewbox, (int, float)) and np.isfinite(viewbox) and viewbox > 0):
+            raise DsvgError(f"PackedSVGStore: viewbox is a finite number > 0; got {viewbox!r}")
+        N, G, S = commands.shape
+        dev = commands.device
+        lens = len_groups.detach().to(torch.int64).clamp(0, S - 1)
+        take = (torch.arange(S, device=dev) - 1).view(1, 1, S)
+        take = (take >= 0) & (take < lens.unsqueeze(-1))                   # the rows between SOS and the first EOS
+        rows = torch.cat([commands.detach().float().unsqueeze(-1), args.detach().float()], dim=-1)[take]
+        if rows.shape[0] == 0:
+            rows = torch.zeros(1, 12, dtype=torch.float32, device=dev)
+        slot_off = torch.zeros(N * G + 1, dtype=torch.int64, device=dev)
+        slot_off[1:] = torch.cumsum(lens.reshape(-1), 0)
+        if N * G * (S - 1) >= 2 ** 31:
+            raise DsvgError("PackedSVGStore: more than 2^31 rows")
+        fill = torch.zeros(N, G, dtype=torch.int64, device=dev) if filling is None else \
+            torch.as_tensor(filling).to(device=dev, dtype=torch.int64).reshape(N, G)
+        label = None if labels is None else torch.as_tensor(labels).to(device=dev, dtype=torch.int64).reshape(N)
+        return cls(rows.contiguous(), slot_off.to(torch.int32), torch.arange(N + 1, dtype=torch.int32, device=dev), fill,
+                   label, G, None, int(lens.max()) if N else 0, int(lens.sum(dim=1).max()) if N else 0, viewbox)
 
     @classmethod
     def from_pkl_dir(cls, data_dir, df, max_num_groups):
@@ -145,13 +197,15 @@ class PackedSVGStore:
                             label=self._np(self.label) if self.label is not None else np.zeros(0, np.int64),
                             has_label=np.array(self.label is not None), G=np.array(self.G),
                             ids=np.array([str(i) for i in self.ids]) if self.ids is not None else np.zeros(0, "U1"),
-                            lims=np.array([self.max_group_len, self.max_total_len]))
+                            lims=np.array([self.max_group_len, self.max_total_len]),
+                            viewbox=np.array(self.viewbox if self.viewbox is not None else 0.0))
 
     @classmethod
     def load(cls, path):
         z = np.load(path)
         return cls(z["rows"], z["slot_off"], z["var_base"], z["filling"], z["label"] if bool(z["has_label"]) else None,
-                   int(z["G"]), list(z["ids"]) if z["ids"].size else None, *[int(v) for v in z["lims"]])
+                   int(z["G"]), list(z["ids"]) if z["ids"].size else None, *[int(v) for v in z["lims"]],
+                   viewbox=float(z["viewbox"]) if "viewbox" in z.files and float(z["viewbox"]) > 0 else None)
 
     @staticmethod
     def _np(a):
@@ -163,7 +217,12 @@ class PackedSVGStore:
 
     @property
     def is_device(self):
-        return isinstance(self.rows, torch.Tensor)
+        return isinstance(self.rows, torch.Tensor) and self.rows.is_cuda
+
+    @property
+    def is_float(self):
+        """the float32 form (raw coordinates and a view box) as opposed to the int16 form (numericalised rows)"""
+        return self.rows.dtype in (np.float32, torch.float32)
 
     def to(self, device):
         device = torch.device(device)
@@ -172,7 +231,7 @@ class PackedSVGStore:
         def mv(a):
             return None if a is None else torch.as_tensor(self._np(a)).to(device).contiguous()
         return PackedSVGStore(mv(self.rows), mv(self.slot_off), mv(self.var_base), mv(self.filling), mv(self.label),
-                              self.G, self.ids, self.max_group_len, self.max_total_len)
+                              self.G, self.ids, self.max_group_len, self.max_total_len, self.viewbox)
 
     def n_variants_of(self, icon):
         vb = self._np(self.var_base)
@@ -205,6 +264,9 @@ class SVGTensorDataset(torch.utils.data.Dataset):
             df = df.sample(frac=train_ratio) if train_ratio < 1.0 else df
             store = PackedSVGStore.from_pkl_dir(data_dir, df, max_num_groups)
         self.df = df
+        if store.is_float:
+            raise DsvgError("the store holds float32 rows: deepsvg_amd.svg_dataset.SVGDataset reads it (it numericalises as it "
+                            "assembles); SVGTensorDataset reads numericalised int16 rows")
         if store.G != max_num_groups:
             raise DsvgError(f"store was packed for {store.G} groups, dataset asks for {max_num_groups}")
         # the reference fails in torch.stack when a tensor is longer than the padded length (pad never truncates,

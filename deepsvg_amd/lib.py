@@ -15,7 +15,9 @@ DSVG_BF16 = 1
 DSVG_I64 = 2          # input dtype of dsvg_sample_points / dsvg_raster_segments / dsvg_canonicalize only
 DSVG_PATHS_GROUPED, DSVG_PATHS_CONCAT = 0, 1   # layouts of dsvg_canonicalize
 DSVG_EXPAND_SPLIT, DSVG_EXPAND_ARCS = 0, 1     # modes of dsvg_paths_expand
-DSVG_RASTER_FILL, DSVG_RASTER_CULL = 1, 2      # flags of dsvg_raster_sweep
+DSVG_STEP_TRANSLATE, DSVG_STEP_SCALE, DSVG_STEP_ROTATE = 0, 1, 2   # step kinds of dsvg_paths_transform / dsvg_assemble_augmented
+DSVG_MAX_STEPS = 16
+DSVG_RASTER_FILL, DSVG_RASTER_CULL = 1, 2     # flags of dsvg_raster_sweep
 DSVG_RASTER_WIDE = 4                           # flag of dsvg_raster_sweep_bwd: a wave per chord, not 16 lanes
 # == DSVG_ABI_VERSION of include/dsvg.h at the time SIGNATURES below was written: load() refuses a library built from another
 # header (a stale .so with the old argument lists would otherwise be called with a stream where a size is expected)
@@ -132,6 +134,9 @@ SIGNATURES = {
     "dsvg_drop_apply": (c_i32, [c_i32, vp, vp, c_i64, c_f32, c_u32, vp, vp]),
     "dsvg_assemble_batch": (c_i32, [vp, c_i64, vp, c_i64, vp, c_i64, c_i32, c_i32, c_i32, c_f32, c_i32, vp, vp, vp,
                                     vp]),
+    "dsvg_assemble_augmented": (c_i32, [vp, c_i64, vp, c_i64, vp, c_i64, c_i32, c_i32, c_i32, c_f32, c_i32, c_i32, c_u32, vp,
+                                        c_i32, vp, vp, vp, vp]),
+    "dsvg_paths_transform": (c_i32, [vp, vp, c_i64, c_i32, c_i32, c_i32, c_u32, vp, c_i32, vp, vp]),
     "dsvg_attention_causal_fwd": (c_i32, [c_i32, vp, vp, vp, c_i64, c_i32, c_i32, c_f32, c_f32, c_u32, vp, vp]),
     "dsvg_attention_causal_bwd": (c_i32, [c_i32, vp, vp, vp, vp, c_i64, c_i32, c_i32, c_f32, c_f32, c_u32, vp, vp]),
     "dsvg_seq_lens": (c_i32, [vp, c_i64, c_i32, c_i32, vp, vp]),

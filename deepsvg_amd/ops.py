@@ -1553,6 +1553,63 @@ def assemble_batch(rows, slot_off, variant, G, L, grouped, want_args=True, want_
 
 
 # ------------------------------------------------------------------------------------------------
+# affine step programs (svglib/svg.py:268-300; csrc/paths_transform.hip)
+# ------------------------------------------------------------------------------------------------
+STEP_KINDS = {"translate": _l.DSVG_STEP_TRANSLATE, "scale": _l.DSVG_STEP_SCALE, "rotate": _l.DSVG_STEP_ROTATE}
+
+
+def _steps(kinds, params, n_items):
+    """kinds: a sequence of K step kinds (0..2); params float32 [n_items, K, 3] -> (K, the packed kinds)"""
+    K = len(kinds)
+    assert 1 <= K <= _l.DSVG_MAX_STEPS and all(0 <= int(k) <= 2 for k in kinds)
+    assert params.dtype == torch.float32 and params.shape == (n_items, K, 3) and params.is_contiguous()
+    packed = 0
+    for k, kind in enumerate(kinds):
+        packed |= int(kind) << (2 * k)
+    return K, packed
+
+
+def paths_transform(commands, args, kinds, params, numericalize=0):
+    """commands [N, G, S] / args [N, G, S, 11] float32, G * S <= 2048; kinds: K step kinds (launch constants), params float32
+    [N, K, 3] on the device -> args [N, G, S, 11] float32 of deepsvg_amd.paths.transform.  One launch, no workspace, nothing
+    read back; include/dsvg.h has the definition"""
+    _chk(commands, args, params)
+    assert commands.dim() == 3 and args.dim() == 4 and args.shape[:3] == commands.shape and args.shape[3] == N_ARGS
+    assert commands.dtype == args.dtype == torch.float32 and commands.is_contiguous() and args.is_contiguous()
+    N, G, S = commands.shape
+    K, packed = _steps(kinds, params, N)
+    out = torch.empty_like(args)
+    _l.check(_l.load().dsvg_paths_transform(commands.data_ptr(), args.data_ptr(), N, G, S, K, packed, params.data_ptr(),
+                                            int(numericalize), out.data_ptr(), _stream()), "dsvg_paths_transform")
+    return out
+
+
+def assemble_augmented(rows, slot_off, variant, G, L, grouped, kinds, params, numericalize=256, want_args=True,
+                       want_rel=False, pad_val=-1.0, args_dim=256):
+    """`assemble_batch` over a float32 store: rows float32 [R, 12], slot_off int32 [n_variants*G + 1], variant int32 [N];
+    item i runs the step program (kinds, params[i]) and the rounding on every row it loads  ->
+    commands f32 [N, G or 1, L], args / args_rel f32 [N, G or 1, L, 11] (None when not wanted)"""
+    _chk(rows, slot_off, variant, params)
+    assert rows.dtype == torch.float32 and rows.dim() == 2 and rows.shape[1] == 12 and rows.is_contiguous()
+    assert slot_off.dtype == torch.int32 and variant.dtype == torch.int32
+    assert slot_off.is_contiguous() and variant.is_contiguous()
+    N = variant.numel()
+    K, packed = _steps(kinds, params, N)
+    Gs = 1 if grouped else G
+    dev = rows.device
+    commands = torch.empty(N, Gs, L, dtype=torch.float32, device=dev)
+    args = torch.empty(N, Gs, L, 11, dtype=torch.float32, device=dev) if want_args else None
+    rel = torch.empty(N, Gs, L, 11, dtype=torch.float32, device=dev) if want_rel else None
+    _l.check(_l.load().dsvg_assemble_augmented(rows.data_ptr(), rows.shape[0], slot_off.data_ptr(), slot_off.numel() - 1,
+                                               variant.data_ptr(), N, G, 1 if grouped else 0, L, float(pad_val),
+                                               int(args_dim), K, packed, params.data_ptr(), int(numericalize),
+                                               commands.data_ptr(), args.data_ptr() if want_args else None,
+                                               rel.data_ptr() if want_rel else None, _stream()),
+             "dsvg_assemble_augmented")
+    return commands, args, rel
+
+
+# ------------------------------------------------------------------------------------------------
 # optimizer / housekeeping
 # ------------------------------------------------------------------------------------------------
 def sumsq(x, out=None):

@@ -43,17 +43,29 @@ csrc/paths_simplify.hip for the whole batch; include/dsvg.h has its definition, 
 float64.  `simplify_heuristic` is ``SVGPath.simplify_heuristic`` (svg_path.py:386-389) as three launches.  The chain back into
 the model, as every data set was preprocessed, is
 ``arcs_to_beziers -> simplify_heuristic -> canonicalize(numericalize=256)``, all of it on the device.
+
+`transform` is the affine map at both ends of that chain, a program of float32 steps in one launch of
+csrc/paths_transform.hip (include/dsvg.h has its definition, tests/paths_transform_ref.py restates it in numpy float32, and
+tests/golden/paths/transform.npz compares with the reference by equality): `normalize` and `zoom` before it
+(``svg.normalize().zoom(0.9)``, svg_dataset.py:112-116), `augment` with ``numericalize`` behind it (``SVGDataset._augment``
+and ``SVG.numericalize(256)``, svg_dataset.py:137-156).  The whole chain of the reference's on-the-fly data set is then
+``arcs_to_beziers -> normalize(viewbox, 24) -> zoom(0.9, viewbox=24) -> canonicalize -> simplify_heuristic(unit=1) ->
+dataset.PackedSVGStore.from_batch(viewbox=24) -> svg_dataset.SVGDataset.batch``, the last link drawing fresh
+augmentation parameters on the device for every batch and applying them while it assembles the model's tensors.
 """
 import math
 
+import numpy as np
 import torch
 
 from . import ops
 from .svgtensor import CMD_ARGS_MASK, C_ID
 
-__all__ = ["canonicalize", "numericalize", "split", "arcs_to_beziers", "simplify", "simplify_heuristic"]
+__all__ = ["canonicalize", "numericalize", "split", "arcs_to_beziers", "simplify", "simplify_heuristic", "transform", "zoom",
+           "rotate", "translate", "normalize", "augment", "augment_params"]
 
 MAX_ROWS = 2048      # G * S rows per icon: the largest icon the model accepts in a two-stage config, 8 groups of 256
+MAX_STEPS = 16       # steps of one `transform`
 
 
 def canonicalize(commands, args, max_num_groups=None, max_seq_len=None, layout="grouped", numericalize=None):
@@ -239,6 +251,183 @@ def simplify_heuristic(commands, args, unit=256 / 24, max_seq_len=None, work_seq
     # an icon invalid at one step is handed on as empty groups, which the later steps pass through: nothing to blank here
     return {"commands": last["commands"], "args": last["args"], "len_groups": last["len_groups"],
             "valid": first["valid"] & fit["valid"] & last["valid"]}
+
+
+def _finite(name, what, v):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+        raise ValueError(f"{name}: {what} is a finite number or a tensor; got {v!r}")
+    return float(v)
+
+
+def _number(name, what, v):
+    return np.float32(_finite(name, what, v))
+
+
+def _pair(name, what, v):
+    """a Python pair (or one number for both coordinates) -> float32 [2]"""
+    if isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool):
+        v = (v, v)
+    if not isinstance(v, (tuple, list, np.ndarray)) or len(v) != 2:
+        raise ValueError(f"{name}: {what} is a pair of numbers or an (N, 2) tensor; got {v!r}")
+    return np.array([_number(name, what, v[0]), _number(name, what, v[1])], dtype=np.float32)
+
+
+def _pack_steps(name, steps, N, device):
+    """steps -> (kinds [K], params float32 [N, K, 3] on the device).  Python parameters are rounded to float32 on the host
+    and reach the device in one copy; tensor parameters are placed with device ops: nothing is read back"""
+    if not isinstance(steps, (list, tuple)) or not 1 <= len(steps) <= MAX_STEPS:
+        raise ValueError(f"{name}: steps is a list of 1..{MAX_STEPS} (kind, parameter) pairs; got "
+                         f"{len(steps) if isinstance(steps, (list, tuple)) else steps!r}")
+    K = len(steps)
+    host = np.zeros((K, 3), dtype=np.float32)
+    late = []                                   # (step, column slice, tensor [N, width])
+    kinds = []
+    for k, step in enumerate(steps):
+        if not isinstance(step, (list, tuple)) or len(step) != 2 or step[0] not in ops.STEP_KINDS:
+            raise ValueError(f"{name}: step {k} is ('translate', v), ('scale', f) or ('rotate', degrees); got {step!r}")
+        kind, v = step
+        kinds.append(ops.STEP_KINDS[kind])
+        if isinstance(v, torch.Tensor):
+            v = v.detach()
+            want = (N, 2) if kind == "translate" else (N,)
+            if tuple(v.shape) != want:
+                raise ValueError(f"{name}: the tensor parameter of step {k} ({kind}) has shape {tuple(v.shape)}, need {want}")
+            if kind == "translate":
+                late.append((k, slice(0, 2), v.to(device=device, dtype=torch.float32)))
+            elif kind == "scale":
+                late.append((k, slice(0, 1), v.to(device=device, dtype=torch.float32).unsqueeze(1)))
+            else:                               # cosine and sine in float64, rounded to float32 (get_rotation_matrix)
+                deg = v.to(device=device, dtype=torch.float64)
+                rad = torch.deg2rad(deg)
+                late.append((k, slice(0, 3), torch.stack([torch.cos(rad), torch.sin(rad), deg], dim=1).float()))
+        elif kind == "translate":
+            host[k, :2] = _pair(name, f"the vector of step {k}", v)
+        elif kind == "scale":
+            host[k, 0] = _number(name, f"the factor of step {k}", v)
+        else:
+            deg = _finite(name, f"the angle of step {k}", v)
+            rad = np.deg2rad(deg)
+            host[k] = (np.cos(rad), np.sin(rad), deg)
+    params = torch.from_numpy(host).to(device).unsqueeze(0).expand(N, K, 3).contiguous()
+    for k, cols, t in late:
+        params[:, k, cols] = t
+    return kinds, params
+
+
+def transform(commands, args, steps, numericalize=None):
+    """An affine step program on every icon of a batch, one launch of csrc/paths_transform.hip: `steps` is a list of 1..16
+    ("translate", v), ("scale", f), ("rotate", degrees), with v a pair or an (N, 2) tensor, f and degrees a number or an
+    (N,) tensor (one value per icon, left on the device: nothing is read back).  commands (N, G, S) with args (N, G, S, 11),
+    or (N, S) with (N, S, 11); G * S <= 2048.  Inputs are detached and read as float32; no gradient.  -> {"commands": the
+    commands as read, "args": the same shape as args, float32}.
+    Every coordinate pair CMD_ARGS_MASK enables on a row before its group's first EOS goes through the steps in order, each
+    add and each multiply rounded to float32 once as the reference's in-place numpy operations are (svglib/geom.py:136-151);
+    a rotate is x' = fl(fl(c x) - fl(s y)), y' = fl(fl(s x) + fl(c y)) with c, s the float64 cosine and sine rounded to
+    float32.  No step is elided or merged.  On an `a` row the end position takes every step, the radii scale steps only, a
+    rotate adds its degrees to the x-axis rotation and the flags are copied - the reference cannot rotate an arc at all, so
+    the arc rule under rotation is this package's own.  Every other slot and every other row (SOS, EOS, `z`, rows at or behind
+    the first EOS) is copied; no row is dropped.  numericalize=n rounds afterwards: clip(round_half_even(v), 0, n - 1) on
+    every enabled slot of a live row, step 7 of `canonicalize`."""
+    if commands.dim() not in (2, 3) or args.dim() != commands.dim() + 1 or args.shape[:-1] != commands.shape \
+            or args.shape[-1] != 11:
+        raise ValueError(f"transform: commands (N, G, S) with args (N, G, S, 11), or (N, S) with (N, S, 11); got "
+                         f"{tuple(commands.shape)} and {tuple(args.shape)}")
+    squeeze = commands.dim() == 2
+    if squeeze:
+        commands, args = commands.unsqueeze(1), args.unsqueeze(1)
+    N, G, S = commands.shape
+    if N < 1:
+        raise ValueError("transform: an empty batch")
+    if G * S < 1 or G * S > MAX_ROWS:
+        raise ValueError(f"transform: {G} x {S} = {G * S} rows per icon, at least 1 and at most {MAX_ROWS}")
+    if numericalize is not None and (isinstance(numericalize, bool) or int(numericalize) < 1):
+        raise ValueError(f"transform: numericalize >= 1 or None; got {numericalize}")
+    kinds, params = _pack_steps("transform", steps, N, commands.device)
+    commands, args = commands.detach().float().contiguous(), args.detach().float().contiguous()
+    out = ops.paths_transform(commands, args, kinds, params, numericalize=0 if numericalize is None else int(numericalize))
+    if squeeze:
+        commands, out = commands.squeeze(1), out.squeeze(1)
+    return {"commands": commands, "args": out}
+
+
+def _neg(v):
+    return -v
+
+
+def _centre(name, viewbox):
+    """the centre of a view box given by its size (a number, or a (width, height) pair): xy + wh / 2 with xy = 0"""
+    return _pair(name, "viewbox", viewbox) * np.float32(0.5)
+
+
+def _zoom_steps(name, factor, center, viewbox):
+    c = _centre(name, viewbox)
+    if center is None:
+        center = c
+    elif not isinstance(center, torch.Tensor):
+        center = _pair(name, "center", center)
+    return [("translate", _neg(c)), ("scale", factor), ("translate", center)]
+
+
+def _normalize_steps(name, viewbox, target):
+    vb = _pair(name, "viewbox", viewbox)
+    t = _number(name, "target", target)
+    if not vb.max() > 0 or not t > 0:
+        raise ValueError(f"{name}: viewbox and target are > 0; got {viewbox!r} and {target!r}")
+    return _zoom_steps(name, t / vb.max(), (t * np.float32(0.5),) * 2, viewbox)     # float32 / float32, as the reference
+
+
+def zoom(commands, args, factor, center=None, viewbox=256):
+    """``SVG.zoom(factor, center)`` (svg.py:281-289) in a view box of size `viewbox` (a number or a (width, height) pair):
+    translate by minus the view-box centre, scale, translate to `center` (default the view-box centre)."""
+    return transform(commands, args, _zoom_steps("zoom", factor, center, viewbox))
+
+
+def rotate(commands, args, degrees, center=None, viewbox=256):
+    """``SVG.rotate(Angle(degrees), center)`` (svg.py:271-279): translate by minus the view-box centre, rotate, translate
+    to `center`.  For arcs see `transform`."""
+    steps = _zoom_steps("rotate", 1.0, center, viewbox)
+    steps[1] = ("rotate", degrees)
+    return transform(commands, args, steps)
+
+
+def translate(commands, args, vec):
+    """``SVG.translate(Point(*vec))`` (svg.py:268-269)."""
+    return transform(commands, args, [("translate", vec)])
+
+
+def normalize(commands, args, viewbox, target=256):
+    """``SVG.normalize(Bbox(target))`` (svg.py:291-300) of icons drawn in a view box of size `viewbox`: a zoom by the
+    float32 quotient target / max(viewbox) from the centre of the view box to the centre of the target box."""
+    return transform(commands, args, _normalize_steps("normalize", viewbox, target))
+
+
+def augment(commands, args, factor, vec, viewbox=256, numericalize=None):
+    """``SVGDataset._augment`` (svg_dataset.py:137-142) with given draws: a zoom by `factor` about the view-box centre and a
+    translation by `vec`, each a number / pair or one value per icon ((N,) and (N, 2) tensors, e.g. of `augment_params`).
+    numericalize=n appends ``SVG.numericalize(n)`` (svg.py:392-394: normalize to the n box, round, clip) to the same launch:
+    with it this is ``SVGDataset.preprocess(svg, augment=True, numericalize=True)``."""
+    steps = _zoom_steps("augment", factor, None, viewbox) + [("translate", vec)]
+    if numericalize is not None:
+        steps += _normalize_steps("augment", viewbox, numericalize)
+    return transform(commands, args, steps, numericalize=numericalize)
+
+
+def augment_params(n, mean=False, viewbox=256, generator=None, device=None):
+    """The draws of ``SVGDataset._augment`` for n icons -> (factor float32 [n], vec float32 [n, 2]): factor = 0.2 u + 0.6 and
+    vec = (5 u - 2.5) * viewbox / 24 with u uniform in [0, 1) (the reference draws in its 24 box); mean=True gives 0.7 and
+    (0, 0) (svg_dataset.py:138-142).  Drawn by the torch generator on `device` (default: the generator's, else "cuda"): the
+    reference's distribution, not the sequence of python's `random`."""
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"augment_params: n is an int >= 1; got {n!r}")
+    vb = float(_number("augment_params", "viewbox", viewbox))
+    if not vb > 0:
+        raise ValueError(f"augment_params: viewbox is > 0; got {viewbox!r}")
+    if device is None:
+        device = generator.device if generator is not None else "cuda"
+    if mean:
+        return torch.full((n,), 0.7, dtype=torch.float32, device=device), torch.zeros(n, 2, dtype=torch.float32, device=device)
+    u = torch.rand(n, 3, dtype=torch.float32, device=device, generator=generator)
+    return 0.2 * u[:, 2] + 0.6, (5.0 * u[:, :2] - 2.5) * (vb / 24.0)
 
 
 def numericalize(args, commands, n=256):

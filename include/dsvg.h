@@ -57,7 +57,9 @@ extern "C" {
  *     Still 19: dsvg_paths_expand added (split and arc conversion for a whole batch).  No exported signature changed, and a
  *     library built without it fails to load by the missing symbol; tests/test_paths_host.py pins 19 for the binding.
  *     Still 19: dsvg_paths_simplify (+ dsvg_paths_simplify_workspace_bytes) added (the Bezier fit of SVGPath.simplify for a
- *     whole batch), on the same terms. */
+ *     whole batch), on the same terms.
+ *     Still 19: dsvg_paths_transform / dsvg_assemble_augmented added (affine step programs for a whole batch, and batch
+ *     assembly over a float32 store with the augmentation applied on load), on the same terms. */
 #define DSVG_ABI_VERSION 19
 
 const char* dsvg_last_error(void);
@@ -883,6 +885,52 @@ int dsvg_assemble_batch(const int16_t* rows, int64_t n_rows, const int32_t* slot
                         const int32_t* variant, int64_t n_items, int32_t G, int32_t grouped, int32_t L,
                         float pad_val, int32_t args_dim, float* commands, float* args, float* args_rel,
                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Affine maps of a batch, and batches augmented as they are assembled (csrc/paths_transform.hip): SVG.translate / rotate /
+ * zoom / normalize / numericalize (deepsvg/svglib/svg.py:268-300, 392-394) and SVGDataset._augment / preprocess
+ * (deepsvg/svg_dataset.py:137-156) on the tensors themselves.  The reference transforms np.float32 points one in-place
+ * operation at a time (svglib/geom.py:136-151), so the definition is a short program of float32 steps
+ * (tests/paths_transform_ref.py restates it in numpy float32, one rounding per operation):
+ *  a transform is a list of K steps, 1 <= K <= DSVG_MAX_STEPS.  The kinds are launch constants: `kinds` holds 2 bits per
+ *    step, step k in bits 2k..2k+1.  The parameters are device memory, fp32 [N, K, 3], one set per item, so random draws
+ *    never leave the device.  Every enabled coordinate pair (x, y) of a live row goes through the steps in order, every
+ *    arithmetic operation rounded to fp32 once, never contracted to a fused multiply-add:
+ *      DSVG_STEP_TRANSLATE (vx, vy, -):  x = x + vx; y = y + vy
+ *      DSVG_STEP_SCALE     (f, -, -):    x = x * f;  y = y * f
+ *      DSVG_STEP_ROTATE    (c, s, deg):  x' = fl(fl(c x) - fl(s y)); y' = fl(fl(s x) + fl(c y)), with c and s the cosine and
+ *                                        sine of the angle, computed by the caller in float64 and rounded to fp32 as
+ *                                        get_rotation_matrix does (geom.py:14-22)
+ *  slots: `m`, `l`: the end position (9:11); `c`: control1, control2 and the end position (5:11); `a`: the end position takes
+ *    every step, the radii (0:2) take scale steps only (Radius.translate is a no-op in the reference), a rotate step adds
+ *    deg to slot 2 as one fp32 add, the flags are copied.  The reference cannot rotate an arc at all: the arc rule under
+ *    rotation is this library's own.  SOS, EOS, `z`, commands outside 0..6 and every slot CMD_ARGS_MASK does not enable
+ *    are copied unchanged.
+ *  numericalize = n > 0 runs after the steps: every enabled slot of a live row becomes clip(round-half-even(v), 0, n - 1),
+ *    the rule of dsvg_canonicalize.
+ *  No step is ever elided or merged, not a scale by exactly 1 and not a translate pair that cancels: (p - 128) + 128 is
+ *    not p in fp32, and the reference executes it.
+ *  The reference's calls as step lists, with view-box size vb, centre c = vb / 2 and every constant an fp32:
+ *    zoom(f, center) = T(-c), S(f), T(center); rotate(deg, center) = T(-c), R(deg), T(center); normalize(target) =
+ *    zoom(fl(target / vb), target / 2); SVG.numericalize(n) = normalize(n), then round and clip; _augment = zoom(f), T(dx, dy).
+ * dsvg_paths_transform: commands [N, G, S] / args [N, G, S, 11] fp32, G * S <= 2048 -> out_args of the same shape.  A group
+ *    ends at its first EOS; rows at or behind it are copied unchanged.  No row is dropped or invalidated.  One workgroup
+ *    per icon, one thread per row.
+ * dsvg_assemble_augmented: dsvg_assemble_batch over a float32 row store [n_rows, 12] (16-byte aligned) with the same
+ *    slot_off / variant addressing and the same outputs; item i of the batch runs parameter set i on every row it loads,
+ *    then the rounding.  args_rel is formed from the transformed and rounded values (the reference calls get_relative_args
+ *    on the numericalised tensor): the previous real command's end position is transformed too.
+ * Both: no atomics, no workspace, no device-to-host read, every output element written: bit-reproducible, capturable. */
+#define DSVG_STEP_TRANSLATE 0
+#define DSVG_STEP_SCALE 1
+#define DSVG_STEP_ROTATE 2
+#define DSVG_MAX_STEPS 16
+int dsvg_paths_transform(const float* commands, const float* args, int64_t N, int32_t G, int32_t S, int32_t K,
+                         uint32_t kinds, const float* params, int32_t numericalize, float* out_args, void* stream);
+int dsvg_assemble_augmented(const float* rows, int64_t n_rows, const int32_t* slot_off, int64_t n_slots,
+                            const int32_t* variant, int64_t n_items, int32_t G, int32_t grouped, int32_t L,
+                            float pad_val, int32_t args_dim, int32_t K, uint32_t kinds, const float* params,
+                            int32_t numericalize, float* commands, float* args, float* args_rel, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Fused FFN sub-block, bf16, d_model = 256 / dim_feedforward = 512 (csrc/ffn_fused.hip):
