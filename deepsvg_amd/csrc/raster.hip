@@ -14,6 +14,11 @@
 //                         `inside` bit at every sequence start.  No atomics, no scratch: bit-reproducible.
 //   dsvg_raster_sweep_nn  the same kernel with one more template flag: the running minimum also keeps the record index of the
 //                         chord that set it (a strict <: of equal d^2 the lowest index), stored where 0 < ink < 1, -1 elsewhere.
+// Layered RGB images (per-group outline / fill / erase, colours and opacities painted in group order):
+//   dsvg_raster_segments_layers  dsvg_raster_segments' kernel under a template flag: closing chords by the group's mode,
+//                                and the record offset of every group's first chord.
+//   dsvg_raster_sweep_layers     the sweep's tiling with three canvas channels per pixel; at a layer's last record the
+//                                workgroup folds: one sqrt, the layer's coverage, the blend, a reset.  Bit-reproducible.
 // The gradient of an image (a pixel's ink depends on the chords only through the distance d to its nearest chord):
 //   dsvg_raster_sweep_bwd     a group of 16 or 64 lanes per chord walks the chord's bounding box, dilated by the reach the sweep
 //                             culls with and clipped to the image, in a fixed order; lanes accumulate the pixels whose saved
@@ -22,6 +27,8 @@
 //   dsvg_raster_segments_bwd  the transpose of dsvg_raster_segments (linear in args): one workgroup per image, the forward's two
 //                             scans, one thread per token gathers its own command's chords, the next row's (whose start point
 //                             is this row's end position) and the closing chords that start or end at it, in float64.
+#include <type_traits>
+
 #include "dsvg_common.h"
 #include "svg_seq.h"
 #include "../../include/dsvg.h"
@@ -43,10 +50,15 @@ inline int64_t raster_cap(int64_t G, int64_t L, int64_t n, int fill) {
 
 // flags word of a record: bit 0 = the first chord of a sequence; bits 1..31 = on a closing chord, how many records back
 // its sub-path's first chord lies (>= n - 1 >= 1), 0 on every other chord
-template <typename T>
+// LAYERS (dsvg_raster_segments_layers): `fill` is per group, read from modes[b, g] (1 = FILL and 2 = ERASE close their
+// sub-paths, every other value is an outline), and layer_first[b, 0..G] receives the record offset of every group's first
+// chord, the count last.  Without LAYERS `modes` and `layer_first` are not touched.
+template <typename T, bool LAYERS>
 __global__ __launch_bounds__(SP_THREADS) void raster_segments_kernel(const T* __restrict__ commands, const T* __restrict__ args,
                                                                      int G, int L, int n, int fill, long long cap,
-                                                                     float* __restrict__ segs, int32_t* __restrict__ seg_counts) {
+                                                                     float* __restrict__ segs, int32_t* __restrict__ seg_counts,
+                                                                     const int32_t* __restrict__ modes,
+                                                                     int32_t* __restrict__ layer_first) {
     __shared__ int pre[SP_MAX_TOK + 1];       // drawing commands of the image before token t
     __shared__ int cl[SP_MAX_TOK + 1];        // sub-paths that end before token t (fill mode; all zero otherwise)
     __shared__ int src[SP_MAX_TOK];           // token of the j-th drawing command
@@ -58,17 +70,32 @@ __global__ __launch_bounds__(SP_THREADS) void raster_segments_kernel(const T* __
     const T* cmd = commands + b * T_;
     const T* arg = args + b * T_ * N_ARGS;
 
+    // whether the sub-paths of token t's group are closed (t < T_)
+    auto closes = [&](int t) -> int {
+        if constexpr (LAYERS) {
+            const int m = modes[b * G + t / L];
+            return m == DSVG_LAYER_FILL || m == DSVG_LAYER_ERASE;
+        } else {
+            return fill;
+        }
+    };
+
     // ---- pass 1: where every command's chords and every sub-path's closing chord go --------------------------------------
     block_flag_scan<SP_MAX_TOK>(T_, pre, wtot, [&](int t) { return is_drawing(cmd, t, T_); });
-    block_flag_scan<SP_MAX_TOK>(T_, cl, wtot, [&](int t) { return subpath_ends(pre, t, T_, L, fill); });
+    if constexpr (LAYERS)
+        block_flag_scan<SP_MAX_TOK>(T_, cl, wtot, [&](int t) { return subpath_ends(pre, t, T_, L, t < T_ ? closes(t) : 0); });
+    else
+        block_flag_scan<SP_MAX_TOK>(T_, cl, wtot, [&](int t) { return subpath_ends(pre, t, T_, L, fill); });
     for (int t = tid; t < T_; t += SP_THREADS)
         if (pre[t + 1] > pre[t]) {
             src[pre[t]] = t;
-            if (fill && (t % L == 0 || pre[t] == pre[t - 1])) first[cl[t]] = t;      // cl[t] sub-paths lie before this one
+            if (closes(t) && (t % L == 0 || pre[t] == pre[t - 1])) first[cl[t]] = t;      // cl[t] sub-paths lie before this one
         }
     __syncthreads();
     const int K = pre[T_];
     if (tid == 0) seg_counts[b] = K * (n - 1) + cl[T_];
+    if constexpr (LAYERS)
+        for (int g = tid; g <= G; g += SP_THREADS) layer_first[b * (G + 1) + g] = pre[g * L] * (n - 1) + cl[g * L];
 
     float* out = segs + b * cap * RS_REC;
     auto put = [&](long long o, float ax, float ay, float bx, float by, int flags) {
@@ -111,7 +138,7 @@ __global__ __launch_bounds__(SP_THREADS) void raster_segments_kernel(const T* __
         put((long long)j * (n - 1) + cl[t] + k, v[0].x, v[0].y, v[1].x, v[1].y, k == 0 && j == pre[g * L] ? 1 : 0);
     }
     // ---- pass 3 (fill): the closing chord of every sub-path, from its last vertex to its first, behind its last chord ----------
-    if (fill)
+    if (LAYERS || fill)
         for (int t = tid; t < T_; t += SP_THREADS)
             if (cl[t + 1] > cl[t]) {
                 const int tf = first[cl[t]];
@@ -254,6 +281,178 @@ __global__ __launch_bounds__(RS_THREADS) void raster_sweep_kernel(const float* _
         ink = fminf(fmaxf(ink, 0.f), 1.f);
         out[(b * size + (row + 4 * r)) * size + col] = ink;
         if (NN) idx[(b * size + (row + 4 * r)) * size + col] = ink > 0.f && ink < 1.f ? mi[r] : -1;
+    }
+}
+
+// Layered images (include/dsvg.h, "Layered images"): raster_sweep_kernel's tiling, chord tiles and chord expressions, with
+// three canvas channels per pixel next to the running minimum and the winding count.  The records of an image are cut into
+// layers by the layer table in LDS (dynamic: NL entries of paint r, g, b, opacity, then NL words `first record | mode << 28`;
+// NL = G, or 1 with COMPOUND; layer g ends where the next one starts, the last one at the count).  A layer without records
+// is skipped.  The walk over a chord tile stops at every layer end that falls into it and folds there: one sqrt per pixel,
+// coverage by the layer's mode, the blend, m and wind reset.  Layer ends depend on the record index alone, so the fold is
+// uniform over the workgroup and the layer's constants live in scalar registers.  An OUTLINE layer visits only the chords
+// within reach of the wave (CULL); FILL and ERASE layers visit every chord for its crossings, as raster_sweep_kernel<true>.
+// A table from another producer cannot lead out of bounds: entries are clamped into 0..count, a layer runs from wherever
+// the layer before it ended, and entries that run backwards give layers without records.
+constexpr int RL_MODE_SHIFT = 28;          // above every record offset (cap < 2^26)
+constexpr int RL_ENTRY_BYTES = 20;
+
+template <bool CULL>
+__global__ __launch_bounds__(RS_THREADS) void raster_sweep_layers_kernel(
+    const float* __restrict__ segs, const int32_t* __restrict__ seg_counts, const int32_t* __restrict__ layer_first,
+    const int32_t* __restrict__ modes, const float* __restrict__ paint, long long cap, int G, int NL, int size, int tiles, float s,
+    float half_w, int compound_mode, int evenodd, float bg0, float bg1, float bg2, float* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float4 rec[RS_CHORDS * 2];
+    __shared__ __attribute__((aligned(16))) float4 box[CULL ? RS_CHORDS : 1];
+    extern __shared__ __attribute__((aligned(16))) float4 lpaint[];
+    int* lfirst = reinterpret_cast<int*>(lpaint + NL);
+    const long long blk = blockIdx.x;
+    const int tx = (int)(blk % tiles), ty = (int)((blk / tiles) % tiles);
+    const long long b = blk / ((long long)tiles * tiles);
+    const int cnt = chamfer_count(seg_counts, b, cap);
+    const float* sg = segs + b * cap * RS_REC;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int col0 = tx * RS_TILE + (wave & 1) * RS_QUAD, row0 = ty * RS_TILE + (wave >> 1) * RS_QUAD;
+    const int col = col0 + (lane & 15), row = row0 + (lane >> 4);
+    const float cx = ((float)col + 0.5f) * s;
+    float cy[RS_PIX], m[RS_PIX], cv0[RS_PIX], cv1[RS_PIX], cv2[RS_PIX];
+    int wind[RS_PIX];
+#pragma unroll
+    for (int r = 0; r < RS_PIX; ++r) {
+        cy[r] = ((float)(row + 4 * r) + 0.5f) * s;
+        m[r] = INFINITY;
+        wind[r] = 0;
+        cv0[r] = bg0; cv1[r] = bg1; cv2[r] = bg2;
+    }
+    const float qx0 = ((float)col0 + 0.5f) * s, qx1 = ((float)(col0 + RS_QUAD - 1) + 0.5f) * s;
+    const float qy0 = ((float)row0 + 0.5f) * s, qy1 = ((float)(row0 + RS_QUAD - 1) + 0.5f) * s;
+    // the culling reach of raster_sweep_kernel, per layer mode
+    const float reach_fill = (0.5f * s) * 1.001f + 0.01f, reach_line = (half_w + 0.5f * s) * 1.001f + 0.01f;
+    const float reach2_fill = reach_fill * reach_fill, reach2_line = reach_line * reach_line;
+
+    // ---- the layer table: values in 0..1 (a NaN reads as 0), offsets in 0..cnt, modes in 0..2 -------------------------------
+    for (int g = tid; g < NL; g += RS_THREADS) {
+        const float* p = paint + (b * G + g) * 4;
+        auto unit = [](float v) { return fminf(fmaxf(v, 0.f), 1.f); };
+        lpaint[g] = make_float4(unit(p[0]), unit(p[1]), unit(p[2]), unit(p[3]));
+        int first = 0, mode = compound_mode;
+        if (compound_mode < 0) {
+            first = min(max(layer_first[b * (G + 1) + g], 0), cnt);
+            mode = modes[b * G + g];
+            mode = mode == DSVG_LAYER_FILL || mode == DSVG_LAYER_ERASE ? mode : DSVG_LAYER_OUTLINE;
+        }
+        lfirst[g] = first | (mode << RL_MODE_SHIFT);
+    }
+    __syncthreads();
+    auto end_of = [&](int g) {        // wave-uniform: the record at which layer g ends
+        return __builtin_amdgcn_readfirstlane(g + 1 < NL ? lfirst[g + 1] & ((1 << RL_MODE_SHIFT) - 1) : cnt);
+    };
+    int g = 0;                        // the layer the next record belongs to: the first one that ends past it
+    while (g < NL && end_of(g) <= 0) ++g;
+
+    for (int j0 = 0; j0 < cnt; j0 += RS_CHORDS) {
+        if (j0) __syncthreads();                       // the tile of the step before has been read
+#pragma unroll
+        for (int h = 0; h < RS_CHORDS / RS_THREADS; ++h) {
+            const int jl = h * RS_THREADS + tid, j = j0 + jl;
+            if (j < cnt) {
+                const float* r = sg + (long long)j * RS_REC;
+                const float ax = r[0], ay = r[1], dx = r[2], dy = r[3];
+                const int fl = __float_as_int(r[4]);
+                const float len2 = fmaf(dx, dx, dy * dy);
+                float by = ay + dy;                    // (the shared end vertex, as raster_sweep_kernel<true> takes it)
+                const int back = (int)((unsigned)fl >> 1);
+                if (back > 0 && back <= j) by = sg[(long long)(j - back) * RS_REC + 1];
+                else if (back == 0 && j + 1 < cnt) by = sg[(long long)(j + 1) * RS_REC + 1];
+                rec[2 * jl] = make_float4(ax, ay, dx, dy);
+                rec[2 * jl + 1] = make_float4(len2 > 1e-30f ? 1.f / len2 : 0.f, by, 0.f, 0.f);
+                if (CULL) box[jl] = make_float4(fminf(ax, ax + dx), fminf(ay, ay + dy), fmaxf(ax, ax + dx), fmaxf(ay, ay + dy));
+            }
+        }
+        __syncthreads();
+        const int c = min(RS_CHORDS, cnt - j0);
+        // one chord against the lane's four pixels; `near` is wave-uniform
+        auto chord = [&](int jl, bool near, auto filled) {
+            const float4 A = rec[2 * jl], B = rec[2 * jl + 1];        // the same address in every lane
+            const float px = cx - A.x;
+#pragma unroll
+            for (int r = 0; r < RS_PIX; ++r) {
+                const float py = cy[r] - A.y;
+                if (filled.value) {
+                    const float e = fmaf(A.z, py, -(A.w * px));
+                    wind[r] += (int)(A.y <= cy[r] && cy[r] < B.y && e > 0.f) - (int)(B.y <= cy[r] && cy[r] < A.y && e < 0.f);
+                }
+                if (near) {
+                    const float t = fminf(fmaxf(fmaf(px, A.z, py * A.w) * B.x, 0.f), 1.f);
+                    const float qx = fmaf(-t, A.z, px), qy = fmaf(-t, A.w, py);
+                    m[r] = fminf(m[r], fmaf(qx, qx, qy * qy));
+                }
+            }
+        };
+        // chords lo..hi - 1 of the tile, all of one layer
+        auto run = [&](int lo, int hi, auto filled) {
+            if (!CULL) {
+                for (int jl = lo; jl < hi; ++jl) chord(jl, true, filled);
+            } else {
+                const float reach2 = filled.value ? reach2_fill : reach2_line;
+                for (int base = lo; base < hi; base += 64) {
+                    bool within = false;
+                    if (base + lane < hi) {
+                        const float4 bb = box[base + lane];
+                        const float gx = fmaxf(fmaxf(bb.x - qx1, qx0 - bb.z), 0.f), gy = fmaxf(fmaxf(bb.y - qy1, qy0 - bb.w), 0.f);
+                        within = !(fmaf(gx, gx, gy * gy) > reach2);
+                    }
+                    unsigned long long mask = __ballot(within);
+                    if (filled.value) {
+                        const int end = min(base + 64, hi);
+                        for (int jl = base; jl < end; ++jl) chord(jl, (mask >> (jl - base)) & 1ull, filled);
+                    } else {
+                        while (mask) {
+                            chord(base + __ffsll((long long)mask) - 1, true, filled);
+                            mask &= mask - 1ull;
+                        }
+                    }
+                }
+            }
+        };
+        int jl = 0;
+        while (jl < c) {                               // g < NL here: the last layer ends at cnt
+            const int le = end_of(g), hi = min(c, le - j0);
+            const int mode = __builtin_amdgcn_readfirstlane(lfirst[g]) >> RL_MODE_SHIFT;
+            if (mode == DSVG_LAYER_OUTLINE) run(jl, hi, std::false_type{});
+            else run(jl, hi, std::true_type{});
+            jl = hi;
+            if (j0 + hi < le) break;                   // the layer goes on in the next tile
+            // ---- the layer is complete: fold it into the canvas ------------------------------------------------------------
+            const float4 P = lpaint[g];
+            const float opacity = P.w;
+            const float p0 = mode == DSVG_LAYER_ERASE ? bg0 : P.x, p1 = mode == DSVG_LAYER_ERASE ? bg1 : P.y;
+            const float p2 = mode == DSVG_LAYER_ERASE ? bg2 : P.z;
+#pragma unroll
+            for (int r = 0; r < RS_PIX; ++r) {
+                const float d = sqrtf(m[r]);
+                float cov;
+                if (mode == DSVG_LAYER_OUTLINE) cov = 0.5f + (half_w - d) / s;
+                else cov = (evenodd ? wind[r] & 1 : wind[r] != 0) ? 0.5f + d / s : 0.5f - d / s;
+                cov = fminf(fmaxf(cov, 0.f), 1.f);
+                const float alpha = opacity * cov;
+                cv0[r] = fmaf(alpha, p0 - cv0[r], cv0[r]);
+                cv1[r] = fmaf(alpha, p1 - cv1[r], cv1[r]);
+                cv2[r] = fmaf(alpha, p2 - cv2[r], cv2[r]);
+                m[r] = INFINITY;
+                wind[r] = 0;
+            }
+            ++g;
+            while (g < NL && end_of(g) <= le) ++g;
+        }
+    }
+    if (col >= size) return;
+    const long long plane = (long long)size * size;
+#pragma unroll
+    for (int r = 0; r < RS_PIX; ++r) {
+        if (row + 4 * r >= size) continue;
+        float* o = out + b * 3 * plane + (long long)(row + 4 * r) * size + col;
+        o[0] = cv0[r]; o[plane] = cv1[r]; o[2 * plane] = cv2[r];
     }
 }
 
@@ -413,25 +612,47 @@ extern "C" int64_t dsvg_raster_workspace_bytes(int64_t n_images, int32_t G, int3
     return n_images * raster_cap(G, L, n, fill) * RS_REC * (int64_t)sizeof(float);
 }
 
-extern "C" int dsvg_raster_segments(int32_t itype, const void* commands, const void* args, int64_t B, int32_t G, int32_t L,
-                                    int32_t n, int32_t fill, void* segs, int64_t segs_bytes, int32_t* seg_counts, void* stream) {
-    DSVG_CHECK_ARG(commands && args && segs && seg_counts, "raster_segments: null pointer");
-    DSVG_CHECK_ARG(itype == DSVG_F32 || itype == DSVG_I64, "raster_segments: itype %d is neither DSVG_F32 nor DSVG_I64", itype);
-    if (sequence_args_ok("raster_segments", "image", B, G, L, n)) return -1;
+namespace {
+// dsvg_raster_segments (modes and layer_first null) and dsvg_raster_segments_layers, refused under the name of the caller
+int segments_launch(const char* name, int32_t itype, const void* commands, const void* args, int64_t B, int32_t G, int32_t L,
+                    int32_t n, int32_t fill, void* segs, int64_t segs_bytes, int32_t* seg_counts, const int32_t* modes,
+                    int32_t* layer_first, void* stream) {
+    DSVG_CHECK_ARG(commands && args && segs && seg_counts, "%s: null pointer", name);
+    DSVG_CHECK_ARG(itype == DSVG_F32 || itype == DSVG_I64, "%s: itype %d is neither DSVG_F32 nor DSVG_I64", name, itype);
+    if (sequence_args_ok(name, "image", B, G, L, n)) return -1;
     const int64_t cap = raster_cap(G, L, n, fill);      // <= 2048 * 64: far below 2^31
     DSVG_CHECK_ARG(segs_bytes >= dsvg_raster_workspace_bytes(B, G, L, n, fill) && ((uintptr_t)segs & 3) == 0,
-                   "raster_segments: buffer of %lld bytes, need %lld (4-byte aligned)", (long long)segs_bytes,
+                   "%s: buffer of %lld bytes, need %lld (4-byte aligned)", name, (long long)segs_bytes,
                    (long long)dsvg_raster_workspace_bytes(B, G, L, n, fill));
     hipStream_t st = (hipStream_t)stream;
-    if (itype == DSVG_I64)
-        hipLaunchKernelGGL(raster_segments_kernel<long long>, dim3((unsigned)B), dim3(SP_THREADS), 0, st,
-                           (const long long*)commands, (const long long*)args, G, L, n, fill ? 1 : 0, (long long)cap,
-                           (float*)segs, seg_counts);
-    else
-        hipLaunchKernelGGL(raster_segments_kernel<float>, dim3((unsigned)B), dim3(SP_THREADS), 0, st, (const float*)commands,
-                           (const float*)args, G, L, n, fill ? 1 : 0, (long long)cap, (float*)segs, seg_counts);
-    DSVG_LAUNCH_CHECK("raster_segments");
+#define RS_SEGMENTS(T, LAYERS)                                                                                              \
+    hipLaunchKernelGGL((raster_segments_kernel<T, LAYERS>), dim3((unsigned)B), dim3(SP_THREADS), 0, st, (const T*)commands,   \
+                       (const T*)args, G, L, n, fill ? 1 : 0, (long long)cap, (float*)segs, seg_counts, modes, layer_first)
+    if (modes) {
+        if (itype == DSVG_I64) RS_SEGMENTS(long long, true);
+        else RS_SEGMENTS(float, true);
+    } else {
+        if (itype == DSVG_I64) RS_SEGMENTS(long long, false);
+        else RS_SEGMENTS(float, false);
+    }
+#undef RS_SEGMENTS
+    DSVG_LAUNCH_CHECK(name);
     return 0;
+}
+}  // namespace
+
+extern "C" int dsvg_raster_segments(int32_t itype, const void* commands, const void* args, int64_t B, int32_t G, int32_t L,
+                                    int32_t n, int32_t fill, void* segs, int64_t segs_bytes, int32_t* seg_counts, void* stream) {
+    return segments_launch("raster_segments", itype, commands, args, B, G, L, n, fill, segs, segs_bytes, seg_counts, nullptr,
+                           nullptr, stream);
+}
+
+extern "C" int dsvg_raster_segments_layers(int32_t itype, const void* commands, const void* args, int64_t B, int32_t G,
+                                           int32_t L, int32_t n, const int32_t* modes, void* segs, int64_t segs_bytes,
+                                           int32_t* seg_counts, int32_t* layer_first, void* stream) {
+    DSVG_CHECK_ARG(modes && layer_first, "raster_segments_layers: null pointer");
+    return segments_launch("raster_segments_layers", itype, commands, args, B, G, L, n, 1, segs, segs_bytes, seg_counts, modes,
+                           layer_first, stream);
 }
 
 namespace {
@@ -487,6 +708,37 @@ extern "C" int dsvg_raster_sweep(const void* segs, const int32_t* seg_counts, in
 extern "C" int dsvg_raster_sweep_nn(const void* segs, const int32_t* seg_counts, int64_t B, int64_t cap, int32_t size,
                                     float stroke_width, int32_t flags, float* out, int32_t* idx, void* stream) {
     return sweep_launch("raster_sweep_nn", segs, seg_counts, B, cap, size, stroke_width, flags, out, idx, true, stream);
+}
+
+extern "C" int dsvg_raster_sweep_layers(const void* segs, const int32_t* seg_counts, const int32_t* layer_first,
+                                        const int32_t* modes, const float* paint, const float* background, int64_t B,
+                                        int64_t cap, int32_t G, int32_t size, float stroke_width, int32_t flags, float* out,
+                                        void* stream) {
+    const int64_t tiles = (size + RS_TILE - 1) / RS_TILE;
+    const bool compound = flags & DSVG_RASTER_COMPOUND;
+    if (sweep_args_ok("raster_sweep_layers", segs && seg_counts && paint && background && out && (compound || (layer_first && modes)),
+                      B, cap, size, stroke_width, flags,
+                      DSVG_RASTER_CULL | DSVG_RASTER_EVENODD | DSVG_RASTER_COMPOUND | (compound ? DSVG_RASTER_FILL : 0),
+                      tiles * tiles))
+        return -1;
+    DSVG_CHECK_ARG(G >= 1 && G <= SP_MAX_TOK, "raster_sweep_layers: G = %d layers per image, need 1..%d", G, SP_MAX_TOK);
+    for (int q = 0; q < 3; ++q)
+        DSVG_CHECK_ARG(background[q] >= 0.f && background[q] <= 1.f, "raster_sweep_layers: background[%d] = %g, need 0..1", q,
+                       (double)background[q]);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)(B * tiles * tiles)), block(RS_THREADS);
+    const float s = 256.f / (float)size, half_w = 0.5f * stroke_width;
+    const int NL = compound ? 1 : G;
+    const int compound_mode = compound ? (flags & DSVG_RASTER_FILL ? DSVG_LAYER_FILL : DSVG_LAYER_OUTLINE) : -1;
+#define RL_LAUNCH(C)                                                                                                          \
+    hipLaunchKernelGGL((raster_sweep_layers_kernel<C>), grid, block, (size_t)NL * RL_ENTRY_BYTES, st, (const float*)segs,      \
+                       seg_counts, layer_first, modes, paint, (long long)cap, G, NL, size, (int)tiles, s, half_w, compound_mode, \
+                       flags & DSVG_RASTER_EVENODD ? 1 : 0, background[0], background[1], background[2], out)
+    if (flags & DSVG_RASTER_CULL) RL_LAUNCH(true);
+    else RL_LAUNCH(false);
+#undef RL_LAUNCH
+    DSVG_LAUNCH_CHECK("raster_sweep_layers");
+    return 0;
 }
 
 extern "C" int dsvg_raster_sweep_bwd(const void* segs, const int32_t* seg_counts, const float* out, const int32_t* idx,

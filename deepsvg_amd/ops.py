@@ -1388,6 +1388,75 @@ def rasterize(commands, args, size=64, stroke_width=3.2, fill=False, n=10, group
     return raster_sweep(segs, seg_counts, size=size, stroke_width=stroke_width, fill=fill, cull=cull)
 
 
+def _chk_layer_tables(name, B, groups, device, **tables):
+    """the per-group tables of the layered rasteriser: modes / layer_first int32, paint f32 [B, groups, 4]"""
+    for key, t in tables.items():
+        want = {"modes": (torch.int32, (B, groups)), "layer_first": (torch.int32, (B, groups + 1)),
+                "paint": (torch.float32, (B, groups, 4))}[key]
+        assert t.dtype == want[0] and tuple(t.shape) == want[1] and t.is_contiguous() and t.device == device, \
+            f"{name}: {key} {want[0]} {list(want[1])} on {device}; got {t.dtype} {list(t.shape)} on {t.device}"
+
+
+def raster_segments_layers(commands, args, modes, n=10, groups=1):
+    """raster_segments with `fill` per group: modes int32 [B, groups] (1 = FILL and 2 = ERASE close their sub-paths, every other
+    value is an outline) -> (segs f32 [B, cap, 5] with the fill-mode cap, seg_counts int32 [B], layer_first int32 [B, groups +
+    1]: the record offset of each group's first chord, the count last).  Records past seg_counts[b] are not written"""
+    _chk(commands, args, modes)
+    B, L = _chk_sequences(commands, args, groups)
+    assert B >= 1
+    _chk_layer_tables("raster_segments_layers", B, groups, commands.device, modes=modes)
+    segs = torch.empty(B, _chord_cap(B, groups, L, n, True), 5, dtype=torch.float32, device=commands.device)
+    seg_counts = torch.empty(B, dtype=torch.int32, device=commands.device)
+    layer_first = torch.empty(B, groups + 1, dtype=torch.int32, device=commands.device)
+    _l.check(_l.load().dsvg_raster_segments_layers(F32 if commands.dtype == torch.float32 else _l.DSVG_I64,
+                                                   commands.data_ptr(), args.data_ptr(), B, groups, L, int(n), modes.data_ptr(),
+                                                   segs.data_ptr(), segs.numel() * 4, seg_counts.data_ptr(),
+                                                   layer_first.data_ptr(), _stream()), "dsvg_raster_segments_layers")
+    return segs, seg_counts, layer_first
+
+
+def raster_sweep_layers(segs, seg_counts, layer_first, modes, paint, background=(1.0, 1.0, 1.0), size=64, stroke_width=3.2,
+                        evenodd=False, compound=None, cull=None):
+    """the records of raster_segments_layers and its tables, paint f32 [B, groups, 4] (r, g, b, opacity; clamped into 0..1 by
+    the kernel) -> f32 [B, 3, size, size], 1 = paper: the layered image include/dsvg.h defines.  `compound` (None, "stroke" or
+    "fill"): the records of raster_segments (same fill) drawn as ONE layer with the paint of group 0; layer_first and modes
+    are then None.  `cull` as raster_sweep: the same bits"""
+    B, cap = _chk_records(segs, seg_counts)
+    assert compound in (None, "stroke", "fill"), f"raster_sweep_layers: compound {compound!r}"
+    _chk(paint)
+    assert paint.dim() == 3, f"raster_sweep_layers: paint [B, groups, 4]; got {list(paint.shape)}"
+    groups = paint.shape[1]
+    _chk_layer_tables("raster_sweep_layers", B, groups, segs.device, paint=paint)
+    flags = _raster_flags(compound == "fill", cull, RASTER_CULL, _l.DSVG_RASTER_CULL)
+    flags |= (_l.DSVG_RASTER_EVENODD if evenodd else 0) | (_l.DSVG_RASTER_COMPOUND if compound else 0)
+    if compound is None:
+        _chk(layer_first, modes)
+        _chk_layer_tables("raster_sweep_layers", B, groups, segs.device, layer_first=layer_first, modes=modes)
+    else:
+        assert layer_first is None and modes is None, "raster_sweep_layers: a compound image has no layer tables"
+    bg = (C.c_float * 3)(*[float(v) for v in background])
+    out = torch.empty(B, 3, int(size), int(size), dtype=torch.float32, device=segs.device)
+    _l.check(_l.load().dsvg_raster_sweep_layers(segs.data_ptr(), seg_counts.data_ptr(), _p(layer_first), _p(modes),
+                                                paint.data_ptr(), C.cast(bg, C.c_void_p), B, cap, groups, int(size),
+                                                float(stroke_width), flags, out.data_ptr(), _stream()),
+             "dsvg_raster_sweep_layers")
+    return out
+
+
+def draw(commands, args, modes, paint, background=(1.0, 1.0, 1.0), size=64, stroke_width=3.2, evenodd=False, compound=None,
+         n=10, groups=1, cull=None):
+    """raster_segments_layers -> raster_sweep_layers (compound: raster_segments -> raster_sweep_layers, modes None): two
+    launches for the whole batch -> f32 [B, 3, size, size]"""
+    if compound is None:
+        segs, seg_counts, layer_first = raster_segments_layers(commands, args, modes, n=n, groups=groups)
+    else:
+        assert modes is None, "draw: a compound image has no mode table"
+        segs, seg_counts = raster_segments(commands, args, n=n, groups=groups, fill=compound == "fill")
+        layer_first = None
+    return raster_sweep_layers(segs, seg_counts, layer_first, modes, paint, background=background, size=size,
+                               stroke_width=stroke_width, evenodd=evenodd, compound=compound, cull=cull)
+
+
 RASTER_BWD_WIDE = False      # the default of raster_sweep_bwd's `wide`: 16 lanes per chord are faster on three of the four
                              # configurations of profiles/raster_grad_bench.log (a wave per chord wins at fill, 128 pixels)
 

@@ -10,9 +10,18 @@ become n - 1 chords each; the view box is 0..256 argument units (``Bbox(256)``),
 (stroke_width / 2 - d) / s, 0, 1) with d the distance to the nearest chord.  Fill mode (no stroke, as
 svglib/svg_primitive.py:34-38): every sub-path is closed, a pixel is inside an image when its non-zero winding number with
 respect to any ONE sequence's chords is not 0, and ink = clamp(0.5 +- d / s, 0, 1).  No atomics: bit-reproducible.
-`rasterize` carries no gradient; `rasterize_with_grad` draws the same bits and does (below).  The reference's per-path
-`filling` values, colours and the visualisation extras of ``draw`` are not drawn; arcs are not either (the reference's own
-sampler skips them).
+`rasterize` carries no gradient; `rasterize_with_grad` draws the same bits and does (below).  Arcs are not drawn (the
+reference's own sampler skips them).
+
+Layered images (`draw`, `palette`; two more entry points of csrc/raster.hip, tests/raster_layers_ref.py restates them in
+float64): the picture the reference shows for an icon - ``SVG.draw`` / ``draw_colored``, with the per-group `filling` of its
+data path (svglib/svg_path.py:29-32: outline, fill, erase).  Group g of an icon is layer g, painted in group order onto a
+canvas of three channels: its coverage is the stroke or fill coverage above computed from the group's OWN chords (fill rule
+non-zero or even-odd), alpha = opacity * coverage, canvas = fmaf(alpha, paint - canvas, canvas) per channel, where paint is
+the group's colour or, for an erase layer, the background - so the counter of an "O", a group of its own since
+`paths.canonicalize`, is a hole again.  ``compound=True`` draws an icon as one <path> with many sub-paths instead.  No
+gradient (`rasterize_with_grad` stays the differentiable path); the dash arrays and the point / handle / box extras of the
+reference's ``draw`` are not drawn.
 
 The gradient of an image with respect to float32 `args` (`rasterize_with_grad`, `image_loss`, `refine_to_images`; three
 more kernels of csrc/raster.hip, tests/raster_grad_ref.py restates them in float64): a pixel's ink depends on the chords only
@@ -31,8 +40,8 @@ import torch
 from . import ops
 from .metrics import _adam_refine, _evaluating, _flat_sequences
 
-__all__ = ["rasterize", "rasterize_with_grad", "image_loss", "refine_to_images", "reconstruction_images", "interpolate",
-           "interpolation_alphas"]
+__all__ = ["rasterize", "draw", "palette", "rasterize_with_grad", "image_loss", "refine_to_images", "reconstruction_images",
+           "interpolate", "interpolation_alphas"]
 
 
 def rasterize(commands, args, size=64, stroke_width=3.2, fill=False, n=10):
@@ -47,9 +56,89 @@ def rasterize(commands, args, size=64, stroke_width=3.2, fill=False, n=10):
 
         layers = rasterize(commands.reshape(N * G, S), args.reshape(N * G, S, 11), fill=True).view(N, G, 1, size, size)
         rgb = 1 - (layers * (1 - torch.rand(N, G, 3, 1, 1, device=layers.device))).amax(1)          # [N, 3, size, size]
+
+    `draw` paints the groups over each other in one sweep, with per-group outline / fill / erase, colours and opacities.
     """
     commands, args, groups = _flat_sequences("rasterize", commands.detach(), args.detach())
     return ops.rasterize(commands, args, size=size, stroke_width=stroke_width, fill=fill, n=n, groups=groups)
+
+
+def _unit_numbers(name, what, values):
+    """Python numbers in 0..1 -> list of float; anything else is refused under the caller's name"""
+    values = [float(v) for v in values]
+    if not all(0.0 <= v <= 1.0 for v in values):          # (a NaN fails both comparisons)
+        raise ValueError(f"{name}: {what} in 0..1; got {values}")
+    return values
+
+
+def _per_group(name, what, value, N, G, last, device):
+    """a table given per group ([G, *last]) or per icon and group ([N, G, *last]) -> float32, broadcastable to [N, G, *last];
+    Python lists are checked against 0..1, tensors are left to the kernel's clamp"""
+    if not torch.is_tensor(value):
+        flat = torch.tensor(value, dtype=torch.float32)
+        _unit_numbers(name, what, flat.flatten().tolist())
+        value = flat
+    value = value.detach().to(device=device, dtype=torch.float32)
+    if tuple(value.shape) not in ((G, *last), (N, G, *last)):
+        raise ValueError(f"{name}: {what} {[G, *last]} or {[N, G, *last]}; got {list(value.shape)}")
+    return value
+
+
+def draw(commands, args, filling=None, colors=None, opacity=1.0, background=1.0, size=64, stroke_width=3.2, fill=False,
+         fill_rule="nonzero", compound=False, n=10):
+    """The groups of every icon painted one over the other into ONE RGB image, the way the reference displays an icon
+    (``SVG.draw``, ``draw_colored``): commands [N, G, S] / args [N, G, S, 11] ([N, S] / [N, S, 11]: G = 1), read, detached and
+    sampled exactly as `rasterize` does -> f32 [N, 3, size, size], 1 = paper white, 0 = black.  No gradient.
+
+    Group g is layer g; layers are painted in group order onto a canvas that starts at `background` (a number or three, in
+    0..1); a group without chords is skipped.
+    `filling`: int [N, G] or [N, G, 1] as the data sets deliver it (``model_args`` with "filling"): 1 = FILL, 2 = ERASE, any
+    other value = OUTLINE; None: every layer OUTLINE, or FILL with ``fill=True``.  It is neither read back nor validated.
+    Coverage of a layer, with d the distance to the nearest chord of ITS group: OUTLINE clamp(0.5 + (stroke_width / 2 - d) / s,
+    0, 1); FILL and ERASE close every sub-path of the group, inside = winding number != 0 (`fill_rule` "nonzero") or odd
+    ("evenodd"), clamp(0.5 +- d / s, 0, 1).
+    Paint: `colors` None (black), [G, 3] or [N, G, 3]; `opacity` a number, [G] or [N, G]; alpha = opacity * coverage, and per
+    channel canvas = fmaf(alpha, paint - canvas, canvas) with paint = the layer's colour, or `background` for an ERASE layer
+    (the hole of a ring: INTEGRATION.md section 6).  Python numbers outside 0..1 raise ValueError; tensors are clamped by the
+    kernel (NaN as 0) and not read back.
+    `compound`: all groups of an icon as ONE layer, the way a single <path> with many sub-paths is drawn - winding counted
+    across the groups, the mode from `fill`, the paint group 0's.  With ``fill=True, fill_rule="evenodd"`` it draws the holes
+    of decoded output, which carries no `filling`.  Not together with `filling`.
+    A one-group black-on-white image is ``1 - rasterize(...)`` bit for bit."""
+    name = "draw"
+    commands, args, G = _flat_sequences(name, commands.detach(), args.detach())
+    N, device = commands.shape[0] // G, commands.device
+    if fill_rule not in ("nonzero", "evenodd"):
+        raise ValueError(f"{name}: fill_rule 'nonzero' or 'evenodd'; got {fill_rule!r}")
+    if compound and filling is not None:
+        raise ValueError(f"{name}: compound=True draws one layer whose mode is `fill`; it takes no `filling`")
+    background = _unit_numbers(name, "background", [background] * 3 if isinstance(background, (int, float)) else background)
+    if len(background) != 3:
+        raise ValueError(f"{name}: background is a number or three; got {len(background)} values")
+    paint = torch.empty(N, G, 4, dtype=torch.float32, device=device)
+    paint[..., :3] = 0.0 if colors is None else _per_group(name, "colors", colors, N, G, (3,), device)
+    paint[..., 3] = (_unit_numbers(name, "opacity", [opacity])[0] if isinstance(opacity, (int, float))
+                     else _per_group(name, "opacity", opacity, N, G, (), device))
+    modes = None
+    if not compound:
+        if filling is None:
+            modes = torch.full((N, G), 1 if fill else 0, dtype=torch.int32, device=device)
+        else:
+            if not torch.is_tensor(filling) or filling.is_floating_point() or tuple(filling.shape) not in ((N, G), (N, G, 1)):
+                raise ValueError(f"{name}: filling is an int tensor {[N, G]} or {[N, G, 1]}; got "
+                                 f"{tuple(filling.shape) if torch.is_tensor(filling) else type(filling).__name__}")
+            modes = filling.detach().reshape(N, G).to(device=device, dtype=torch.int32).contiguous()
+    return ops.draw(commands, args, modes, paint, background=background, size=size, stroke_width=stroke_width,
+                    evenodd=fill_rule == "evenodd", compound=("fill" if fill else "stroke") if compound else None, n=n, groups=G)
+
+
+def palette(G, device=None):
+    """G distinct colours for ``draw_colored``-style pictures -> f32 [G, 3]: hues evenly spaced around the colour circle from
+    a fixed start, at saturation 0.7 and value 0.85 (dark enough to read on white paper)"""
+    hue = (torch.arange(G, dtype=torch.float32) / max(G, 1) + 0.58) % 1.0
+    k = (torch.tensor([5.0, 3.0, 1.0]).view(1, 3) + hue.view(-1, 1) * 6.0) % 6.0
+    rgb = 0.85 * (1.0 - 0.7 * torch.minimum(torch.minimum(k, 4.0 - k), torch.ones(())).clamp(min=0.0))
+    return rgb.to(device) if device is not None else rgb
 
 
 class _Rasterize(torch.autograd.Function):

@@ -59,7 +59,9 @@ extern "C" {
  *     Still 19: dsvg_paths_simplify (+ dsvg_paths_simplify_workspace_bytes) added (the Bezier fit of SVGPath.simplify for a
  *     whole batch), on the same terms.
  *     Still 19: dsvg_paths_transform / dsvg_assemble_augmented added (affine step programs for a whole batch, and batch
- *     assembly over a float32 store with the augmentation applied on load), on the same terms. */
+ *     assembly over a float32 store with the augmentation applied on load), on the same terms.
+ *     Still 19: dsvg_raster_segments_layers / dsvg_raster_sweep_layers added (layered RGB images: per-group outline, fill and
+ *     erase, colours and opacities), on the same terms. */
 #define DSVG_ABI_VERSION 19
 
 const char* dsvg_last_error(void);
@@ -667,6 +669,50 @@ int dsvg_raster_sweep_bwd(const void* segs, const int32_t* seg_counts, const flo
                           int64_t B, int64_t cap, int32_t size, float stroke_width, int32_t flags, float* dsegs, void* stream);
 int dsvg_raster_segments_bwd(const float* commands, const float* dsegs, const int32_t* seg_counts, int64_t B, int32_t G,
                              int32_t L, int32_t n, int32_t fill, float* dargs, void* stream);
+/* Layered images: the G groups of an icon painted one over the other into ONE RGB image, each as an outline, filled, or as
+ * an erase path (the per-group `filling` of the reference's data path, deepsvg/svglib/svg_path.py:29-32), with a colour and
+ * an opacity per group - what SVG.draw / draw_colored show (svglib/svg.py:172-221).  Geometry, pixels, the distance to a
+ * chord and the half-open crossing rule are those of the section above; tests/raster_layers_ref.py restates the rest in
+ * float64.  No gradient.  The definition:
+ *  layers: group g of an image is layer g; layers are painted in group order onto a canvas of three channels that starts at
+ *    `background`; 1 = paper white, 0 = black.  A layer without chords is skipped.  All arithmetic is fp32.
+ *  mode of a layer (modes int32 [B, G]): DSVG_LAYER_FILL, DSVG_LAYER_ERASE, every other value DSVG_LAYER_OUTLINE.
+ *  coverage of layer g, with d_g the distance to the nearest chord of group g alone:
+ *    OUTLINE: cov = clamp(0.5 + (stroke_width / 2 - d_g) / s, 0, 1); no closing chords.
+ *    FILL, ERASE: every sub-path of the group is closed by one chord; w = the winding number with respect to the group's own
+ *      chords; inside = w != 0, or w odd with DSVG_RASTER_EVENODD; cov = clamp(0.5 + d_g / s, 0, 1) inside and clamp(0.5 -
+ *      d_g / s, 0, 1) outside.
+ *  paint (paint fp32 [B, G, 4]: r, g, b, opacity; the kernel clamps every value into 0..1 and reads a NaN as 0): alpha =
+ *    opacity * cov; p = the layer's colour, or `background` for an ERASE layer; per channel canvas = fmaf(alpha, p - canvas,
+ *    canvas).  Black on white at opacity 1 gives fmaf(cov, -1, 1), the correctly rounded 1 - cov: a one-group image is
+ *    1 - dsvg_raster_sweep's, bit for bit.
+ *  DSVG_RASTER_COMPOUND: all groups of an image are ONE layer, as a single <path> with many sub-paths is drawn: w counts the
+ *    chords of all groups, d runs over all of them, the mode is FILL with DSVG_RASTER_FILL and OUTLINE without, the paint is
+ *    group 0's.  With DSVG_RASTER_FILL | DSVG_RASTER_EVENODD a sub-path inside another one is a hole.
+ *  raster_segments_layers: dsvg_raster_segments with `fill` per group: closing chords behind the sub-paths of FILL and ERASE
+ *    groups only.  Same record format; `segs` holds dsvg_raster_workspace_bytes(B, G, L, n, 1) bytes.  Also writes layer_first
+ *    int32 [B, G + 1]: the record offset of each group's first chord, seg_counts[b] last; a group without chords has the
+ *    entry of the group after it.  With modes all OUTLINE the records are those of dsvg_raster_segments(fill = 0), with all
+ *    FILL those of fill = 1, bit for bit.
+ *  raster_sweep_layers: segs / seg_counts / layer_first / modes as above and paint -> out fp32 [B, 3, size, size].  `cap` is the
+ *    record capacity per image, G the number of groups (1..2048), `background` three HOST floats in 0..1.  flags:
+ *    DSVG_RASTER_CULL (same bits with and without: an OUTLINE layer skips chords out of reach, FILL and ERASE layers skip
+ *    their distance work only), DSVG_RASTER_EVENODD, DSVG_RASTER_COMPOUND (records from dsvg_raster_segments with the same
+ *    fill; layer_first and modes are not read and may be null), DSVG_RASTER_FILL (with COMPOUND only).  The layer table of an
+ *    image sits in LDS (20 bytes per group).  layer_first from any producer is clamped into 0..seg_counts[b]; layer g takes
+ *    the records from the end of the layer before it to layer_first[g + 1] (the last one to the count), so no table leads out
+ *    of bounds.  No atomics: bit-reproducible. */
+#define DSVG_LAYER_OUTLINE 0
+#define DSVG_LAYER_FILL 1
+#define DSVG_LAYER_ERASE 2
+#define DSVG_RASTER_EVENODD 8
+#define DSVG_RASTER_COMPOUND 16
+int dsvg_raster_segments_layers(int32_t itype, const void* commands, const void* args, int64_t B, int32_t G, int32_t L,
+                                int32_t n, const int32_t* modes, void* segs, int64_t segs_bytes, int32_t* seg_counts,
+                                int32_t* layer_first, void* stream);
+int dsvg_raster_sweep_layers(const void* segs, const int32_t* seg_counts, const int32_t* layer_first, const int32_t* modes,
+                             const float* paint, const float* background, int64_t B, int64_t cap, int32_t G, int32_t size,
+                             float stroke_width, int32_t flags, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Canonical path order of a batch (csrc/paths.hip): SVG.canonicalize() (deepsvg/svglib/svg.py:333-349) applied to
