@@ -163,13 +163,13 @@ __global__ __launch_bounds__(CP_THREADS) void canonicalize_kernel(
         if (cnt == 1) {
             t = krow[j0];
             const float sx = ex[t - 1], sy = ey[t - 1], fx = ex[t], fy = ey[t];
-            cw = sx < fx || (sx == fx && sy <= fy);
+            cw = single_command_clockwise(sx, sy, fx, fy);
         } else {
             double det = 0.0;
             int j = best;
             for (int i = 0; i < cnt; ++i) {
                 t = krow[j0 + j];
-                det += (double)ex[t - 1] * (double)ey[t] - (double)ey[t - 1] * (double)ex[t];
+                det += orientation_term(ex[t - 1], ey[t - 1], ex[t], ey[t]);
                 if (++j == cnt) j = 0;
             }
             cw = det >= 0.0;

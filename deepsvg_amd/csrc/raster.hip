@@ -34,12 +34,7 @@
 #include "../../include/dsvg.h"
 
 namespace {
-constexpr int RS_REC = 5;                 // words of a chord record: ax, ay, bx - ax, by - ay, flags
-constexpr int RS_THREADS = 256;
-constexpr int RS_TILE = 32;               // pixels per side of a workgroup's tile
-constexpr int RS_QUAD = 16;               // pixels per side of a wave's quadrant
-constexpr int RS_PIX = 4;                 // pixels of a lane: rows ly, ly + 4, ly + 8, ly + 12 of its quadrant
-constexpr int RS_CHORDS = 512;            // chords per LDS tile (16 KiB of records, 8 KiB of boxes when culling)
+// (the record and tile constants RS_* are in svg_seq.h, shared with csrc/paths_fill.hip)
 constexpr int RS_MAX_SIZE = 4096;
 
 // chords an image can hold: n - 1 per token, and in fill mode one closing chord per sub-path (two sub-paths of a sequence
@@ -200,11 +195,7 @@ __global__ __launch_bounds__(RS_THREADS) void raster_sweep_kernel(const float* _
                 const int fl = __float_as_int(r[4]);
                 const float len2 = fmaf(dx, dx, dy * dy);
                 float by = ay + dy;
-                if (FILL) {       // records that break the rule of include/dsvg.h keep ay + dy: in bounds, not watertight
-                    const int back = (int)((unsigned)fl >> 1);
-                    if (back > 0 && back <= j) by = sg[(long long)(j - back) * RS_REC + 1];
-                    else if (back == 0 && j + 1 < cnt) by = sg[(long long)(j + 1) * RS_REC + 1];
-                }
+                if (FILL) by = chord_end_y(sg, j, cnt, ay, dy, fl);
                 rec[2 * jl] = make_float4(ax, ay, dx, dy);
                 rec[2 * jl + 1] = make_float4(len2 > 1e-30f ? 1.f / len2 : 0.f, by, __int_as_float(fl), 0.f);
                 if (CULL) box[jl] = make_float4(fminf(ax, ax + dx), fminf(ay, ay + dy), fmaxf(ax, ax + dx), fmaxf(ay, ay + dy));
@@ -227,9 +218,7 @@ __global__ __launch_bounds__(RS_THREADS) void raster_sweep_kernel(const float* _
             for (int r = 0; r < RS_PIX; ++r) {
                 const float py = cy[r] - A.y;
                 if (FILL) {
-                    // the crossing of the chord's line with the pixel's row lies at x > cx: e > 0 going down the image
-                    // (ay <= cy < by), e < 0 going up
-                    const float e = fmaf(A.z, py, -(A.w * px));
+                    const float e = chord_side(A.z, A.w, px, py);
                     wind[r] += (int)(A.y <= cy[r] && cy[r] < B.y && e > 0.f) - (int)(B.y <= cy[r] && cy[r] < A.y && e < 0.f);
                 }
                 if (near) {
@@ -360,10 +349,7 @@ __global__ __launch_bounds__(RS_THREADS) void raster_sweep_layers_kernel(
                 const float ax = r[0], ay = r[1], dx = r[2], dy = r[3];
                 const int fl = __float_as_int(r[4]);
                 const float len2 = fmaf(dx, dx, dy * dy);
-                float by = ay + dy;                    // (the shared end vertex, as raster_sweep_kernel<true> takes it)
-                const int back = (int)((unsigned)fl >> 1);
-                if (back > 0 && back <= j) by = sg[(long long)(j - back) * RS_REC + 1];
-                else if (back == 0 && j + 1 < cnt) by = sg[(long long)(j + 1) * RS_REC + 1];
+                const float by = chord_end_y(sg, j, cnt, ay, dy, fl);      // (as raster_sweep_kernel<true> takes it)
                 rec[2 * jl] = make_float4(ax, ay, dx, dy);
                 rec[2 * jl + 1] = make_float4(len2 > 1e-30f ? 1.f / len2 : 0.f, by, 0.f, 0.f);
                 if (CULL) box[jl] = make_float4(fminf(ax, ax + dx), fminf(ay, ay + dy), fmaxf(ax, ax + dx), fmaxf(ay, ay + dy));
@@ -379,7 +365,7 @@ __global__ __launch_bounds__(RS_THREADS) void raster_sweep_layers_kernel(
             for (int r = 0; r < RS_PIX; ++r) {
                 const float py = cy[r] - A.y;
                 if (filled.value) {
-                    const float e = fmaf(A.z, py, -(A.w * px));
+                    const float e = chord_side(A.z, A.w, px, py);
                     wind[r] += (int)(A.y <= cy[r] && cy[r] < B.y && e > 0.f) - (int)(B.y <= cy[r] && cy[r] < A.y && e < 0.f);
                 }
                 if (near) {

@@ -1,10 +1,11 @@
 // Sequences of drawing commands on the device, stated once for csrc/metrics.hip (sample_points and its backward),
 // csrc/raster.hip (the chords of an image and their backward), csrc/paths.hip (canonical path order),
 // csrc/paths_expand.hip (commands split, arcs converted), csrc/paths_simplify.hip (Beziers fitted), csrc/paths_transform.hip
-// (affine step programs) and csrc/assemble.hip (batch assembly): the command vocabulary, the argument mask
-// and the argument columns of SVGTensor (deepsvg/difflib/tensor.py:8-41), the ballot prefix scan that gives every drawing
-// command its output offset and the scans built on it, the prefix sum of counts for rows that become several, the count
-// clamp of a cloud, and the curve a drawing command draws with its transpose.
+// (affine step programs), csrc/paths_fill.hip (overlap counts and filling) and csrc/assemble.hip (batch assembly): the command
+// vocabulary, the argument mask and the argument columns of SVGTensor (deepsvg/difflib/tensor.py:8-41), the ballot prefix scan
+// that gives every drawing command its output offset and the scans built on it, the prefix sum of counts for rows that become
+// several, the count clamp of a cloud, the chord record with its crossing test, the orientation of a path, and the curve a
+// drawing command draws with its transpose.
 //
 // The contracts that live here: the rasteriser's vertices are sample_points' points, and the backward kernels run on the
 // forward's offsets.  A drawing command (`l`, `c`) of token t starts at the end position of the row before it, whatever that
@@ -131,6 +132,64 @@ __device__ __forceinline__ bool subpath_ends(const int* pre, int t, const int& T
 // ---- the count clamp: the points (records) in use of cloud b, whatever n[b] holds ------------------------------------
 __device__ __forceinline__ int chamfer_count(const int32_t* n, long long b, long long cap) {
     return (int)min((long long)max(n[b], 0), cap);
+}
+
+// ---- chord records and the crossing test (csrc/raster.hip writes and sweeps them, csrc/paths_fill.hip counts with them) ----
+constexpr int RS_REC = 5;                 // words of a chord record: ax, ay, bx - ax, by - ay, flags
+constexpr int RS_THREADS = 256;
+constexpr int RS_TILE = 32;               // pixels per side of a workgroup's tile
+constexpr int RS_QUAD = 16;               // pixels per side of a wave's quadrant
+constexpr int RS_PIX = 4;                 // pixels of a lane: rows ly, ly + 4, ly + 8, ly + 12 of its quadrant
+constexpr int RS_CHORDS = 512;            // chords per LDS tile (16 KiB of records, 8 KiB of boxes when culling)
+
+// The y of record j's end vertex AS THE NEXT CHORD HOLDS IT: the a of the record after it, on a closing chord (flags word fl,
+// bits 1.. = records back) the a of its sub-path's first record.  ay + dy is that value only up to rounding, and the half-open
+// rule below is watertight only when a shared vertex is one number.  Records that break the rule of include/dsvg.h keep
+// ay + dy: in bounds, not watertight.
+__device__ __forceinline__ float chord_end_y(const float* sg, int j, int cnt, float ay, float dy, int fl) {
+    float by = ay + dy;
+    const int back = (int)((unsigned)fl >> 1);
+    if (back > 0 && back <= j) by = sg[(long long)(j - back) * RS_REC + 1];
+    else if (back == 0 && j + 1 < cnt) by = sg[(long long)(j + 1) * RS_REC + 1];
+    return by;
+}
+
+// The sign test of the crossing rule.  The chord a -> b (dx, dy = b - a as stored; ay, by its vertices' y, by from chord_end_y)
+// adds to the winding count of the sample at a + (px, py) on the row cy, on a ray towards +x with the half-open rule: the
+// crossing of the chord's line with the row lies at x > cx when e > 0 going down the image (ay <= cy < by), e < 0 going up
+// (by <= cy < ay).  e = fmaf(dx, py, -p) with p = fl(dy px) is the sweeps' test.  It rounds one product and not the other, so for
+// a sample ON the chord's line (an end position of an integer icon under an integer sample centre, a chord's midpoint) it
+// returns the rounding residual of p, of either sign: a crossing that lies at x == cx is counted or not by chance.  In an
+// image that cannot be seen (the coverage there is 0.5 -+ d / s with d zero up to rounding); a sample count is off by one.
+// COMPENSATED (csrc/paths_fill.hip only) subtracts that residual, r = fmaf(dy, px, -p) = dy px - p, which fp32 holds exactly
+// unless it underflows (|dy px| below 2^-102: r is then flushed and e is the sweeps' value): e = fl(fl(dx py - p) - r).
+// With E = dx py - dy px the true value for the fp32 px, py: E == 0 gives e == 0 (dx py - p equals r, a float, and both
+// roundings are exact); otherwise e has the sign of E or is 0 (rounding is monotone), and 0 only where |E| is below the
+// rounding of dx py - p while that is about |r| <= ulp(p) / 2: |E| <= 2^-24 ulp(p) <= 2^-47 |dy px| - far inside the band in
+// which the rounding of px and py decides anyway.
+template <bool COMPENSATED = false>
+__device__ __forceinline__ float chord_side(float dx, float dy, float px, float py) {
+    if constexpr (COMPENSATED) {
+        const float p = dy * px;
+        return fmaf(dx, py, -p) - fmaf(dy, px, -p);
+    } else {
+        return fmaf(dx, py, -(dy * px));
+    }
+}
+// (The half-open count itself, (ay <= cy && cy < by && e > 0) - (by <= cy && cy < ay && e < 0), stays written out in the
+// three kernels: as a function, with or without the sign test inside, hipcc schedules the two fill sweeps without culling
+// differently.)
+
+// ---- orientation (SVGPath.is_clockwise, svglib/svg_path.py:244-252) ------------------------------------------------------
+// one command's term of the determinant sum, start (sx, sy) -> end (fx, fy): float64, no fused multiply-add (tests/paths_ref.py
+// and tests/paths_fill_ref.py restate it operation by operation)
+__device__ __forceinline__ double orientation_term(float sx, float sy, float fx, float fy) {
+#pragma clang fp contract(off)
+    return (double)sx * (double)fy - (double)sy * (double)fx;
+}
+// a path of one command is clockwise when start <= end lexicographically, any other when the sum of its terms is >= 0
+__device__ __forceinline__ bool single_command_clockwise(float sx, float sy, float fx, float fy) {
+    return sx < fx || (sx == fx && sy <= fy);
 }
 
 // ---- curve evaluation ----------------------------------------------------------------------------------------------------

@@ -21,6 +21,7 @@ DSVG_RASTER_FILL, DSVG_RASTER_CULL = 1, 2     # flags of dsvg_raster_sweep
 DSVG_RASTER_WIDE = 4                           # flag of dsvg_raster_sweep_bwd: a wave per chord, not 16 lanes
 DSVG_RASTER_EVENODD, DSVG_RASTER_COMPOUND = 8, 16      # flags of dsvg_raster_sweep_layers
 DSVG_LAYER_OUTLINE, DSVG_LAYER_FILL, DSVG_LAYER_ERASE = 0, 1, 2       # the mode table of the layered rasteriser
+DSVG_FILLING_EVENODD, DSVG_FILLING_ORIENTATION = 0, 1                 # rules of dsvg_filling_from_counts
 # == DSVG_ABI_VERSION of include/dsvg.h at the time SIGNATURES below was written: load() refuses a library built from another
 # header (a stale .so with the old argument lists would otherwise be called with a stream where a size is expected)
 ABI_VERSION = 19
@@ -183,6 +184,8 @@ SIGNATURES = {
     "dsvg_raster_segments_layers": (c_i32, [c_i32, vp, vp, c_i64, c_i32, c_i32, c_i32, vp, vp, c_i64, vp, vp, vp]),
     "dsvg_raster_sweep_layers": (c_i32, [vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_i32, vp, vp]),
     "dsvg_canonicalize": (c_i32, [c_i32, vp, vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "dsvg_overlap_counts": (c_i32, [vp, vp, vp, c_i64, c_i64, c_i32, c_i32, c_i32, vp, vp, vp]),
+    "dsvg_filling_from_counts": (c_i32, [c_i32, vp, vp, vp, vp, vp, c_i64, c_i32, c_i32, C.c_double, c_i32, vp, vp, vp, vp, vp, vp]),
     "dsvg_paths_expand": (c_i32, [c_i32, vp, vp, c_i64, c_i32, c_i32, c_i32, c_i32, C.c_double, c_i32, vp, vp, vp, vp, vp, vp, vp]),
     "dsvg_paths_simplify_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
     "dsvg_paths_simplify": (c_i32, [vp, vp, c_i64, c_i32, c_i32, c_i32, C.c_double, C.c_double, C.c_double, c_i32, C.c_double, vp,

@@ -1541,6 +1541,52 @@ def canonicalize(commands, args, g_out, s_out, concat=False, numericalize=0):
             "reversed": rev, "valid": valid}
 
 
+FILLING_RULES = {"evenodd": _l.DSVG_FILLING_EVENODD, "orientation": _l.DSVG_FILLING_ORIENTATION}
+
+
+def overlap_counts(segs, seg_counts, layer_first, samples=128, evenodd=False):
+    """the records and layer table of raster_segments_layers built with every mode FILL -> (area int32 [B, G], inter int32 [B,
+    G, G]): the samples, of samples x samples pixel centres, inside each group and inside each pair of groups (non-zero
+    winding, or odd with `evenodd`); include/dsvg.h has the definition.  Integer atomics into zeroed tables: bit-reproducible"""
+    B, cap = _chk_records(segs, seg_counts)
+    _chk(layer_first)
+    assert layer_first.dim() == 2, f"overlap_counts: layer_first [B, G + 1]; got {list(layer_first.shape)}"
+    groups = layer_first.shape[1] - 1
+    _chk_layer_tables("overlap_counts", B, groups, segs.device, layer_first=layer_first)
+    area = torch.zeros(B, groups, dtype=torch.int32, device=segs.device)
+    inter = torch.zeros(B, groups, groups, dtype=torch.int32, device=segs.device)
+    _l.check(_l.load().dsvg_overlap_counts(segs.data_ptr(), seg_counts.data_ptr(), layer_first.data_ptr(), B, cap, groups,
+                                           int(samples), int(bool(evenodd)), area.data_ptr(), inter.data_ptr(), _stream()),
+             "dsvg_overlap_counts")
+    return area, inter
+
+
+def filling_from_counts(area, inter, commands, args, participating, threshold=0.9, rule="evenodd"):
+    """area int32 [N, G] / inter int32 [N, G, G] of overlap_counts, commands [N, G, S] / args [N, G, S, 11] (both float32 or both
+    int64), participating bool [N, G] -> the dict of deepsvg_amd.paths.compute_filling without the counts: "filling" int64 [N,
+    G], "depth" / "parent" int32, "clockwise" bool, "paint_order" int64 [N, G].  One launch; include/dsvg.h has the definition"""
+    _chk(area, inter, commands, args, participating)
+    assert commands.dim() == 3 and args.dim() == 4 and args.shape[:3] == commands.shape and args.shape[3] == N_ARGS
+    assert commands.dtype == args.dtype and commands.dtype in (torch.float32, torch.int64)
+    assert commands.is_contiguous() and args.is_contiguous()
+    N, G, S = commands.shape
+    assert area.dtype == torch.int32 and area.shape == (N, G) and area.is_contiguous()
+    assert inter.dtype == torch.int32 and inter.shape == (N, G, G) and inter.is_contiguous()
+    assert participating.dtype == torch.bool and participating.shape == (N, G) and participating.is_contiguous()
+    dev = commands.device
+    filling = torch.empty(N, G, dtype=torch.int64, device=dev)
+    depth = torch.empty(N, G, dtype=torch.int32, device=dev)
+    parent = torch.empty(N, G, dtype=torch.int32, device=dev)
+    clockwise = torch.empty(N, G, dtype=torch.bool, device=dev)
+    paint_order = torch.empty(N, G, dtype=torch.int64, device=dev)
+    _l.check(_l.load().dsvg_filling_from_counts(F32 if commands.dtype == torch.float32 else _l.DSVG_I64, area.data_ptr(),
+                                                inter.data_ptr(), commands.data_ptr(), args.data_ptr(),
+                                                participating.data_ptr(), N, G, S, float(threshold), FILLING_RULES[rule],
+                                                filling.data_ptr(), depth.data_ptr(), parent.data_ptr(), clockwise.data_ptr(),
+                                                paint_order.data_ptr(), _stream()), "dsvg_filling_from_counts")
+    return {"filling": filling, "depth": depth, "parent": parent, "clockwise": clockwise, "paint_order": paint_order}
+
+
 def paths_expand(commands, args, s_out, arcs=False, n=0, max_dist=0.0, include_lines=True):
     """commands [N, G, S] / args [N, G, S, 11] float32, G * S <= 2048 and G * s_out <= 2048 -> the dict of
     deepsvg_amd.paths.split (n >= 1, or n = 0 with max_dist > 0) or, with arcs=True, of deepsvg_amd.paths.arcs_to_beziers:

@@ -52,6 +52,17 @@ and ``SVG.numericalize(256)``, svg_dataset.py:137-156).  The whole chain of the 
 ``arcs_to_beziers -> normalize(viewbox, 24) -> zoom(0.9, viewbox=24) -> canonicalize -> simplify_heuristic(unit=1) ->
 dataset.PackedSVGStore.from_batch(viewbox=24) -> svg_dataset.SVGDataset.batch``, the last link drawing fresh
 augmentation parameters on the device for every batch and applying them while it assembles the model's tensors.
+
+`compute_filling` gives a decoded batch the per-group ``filling`` (0 = OUTLINE, 1 = FILL, 2 = ERASE) that `render.draw`,
+``PackedSVGStore.from_batch`` and ``SVGDataset`` take and that tensors do not carry: ``SVGPathGroup.compute_filling`` over
+``overlap_graph`` (svglib/svg_primitive.py:392-441), which ``SVG.canonicalize_new`` runs on all sub-paths of an icon
+(svg.py:312-331).  The reference measures overlap with shapely polygons on the host, one icon at a time; `overlap` is this
+package's own measure: sample counts on the rasteriser's chord records and crossing rule, one launch of csrc/paths_fill.hip
+behind the rasteriser's segment pass.  A third launch walks the cover graph of every icon.  include/dsvg.h has the
+definition, tests/paths_fill_ref.py restates it in float64, and tests/golden/paths/filling.npz holds the reference's own
+walk on given graphs.  The chain for decoded output is ``greedy_sample -> canonicalize -> compute_filling -> render.draw``.
+Out of scope: ``SVG.group_overlapping_paths`` (the regrouping into groups of several sub-paths; "parent" and "depth" are what
+it needs), arcs, and any change to `draw` itself.
 """
 import math
 
@@ -62,10 +73,12 @@ from . import ops
 from .svgtensor import CMD_ARGS_MASK, C_ID
 
 __all__ = ["canonicalize", "numericalize", "split", "arcs_to_beziers", "simplify", "simplify_heuristic", "transform", "zoom",
-           "rotate", "translate", "normalize", "augment", "augment_params"]
+           "rotate", "translate", "normalize", "augment", "augment_params", "overlap", "compute_filling"]
 
 MAX_ROWS = 2048      # G * S rows per icon: the largest icon the model accepts in a two-stage config, 8 groups of 256
 MAX_STEPS = 16       # steps of one `transform`
+MAX_FILL_GROUPS = 32                 # groups per icon of `overlap` / `compute_filling`: one mask word
+MIN_SAMPLES, MAX_SAMPLES = 8, 1024   # samples per side of `overlap`
 
 
 def canonicalize(commands, args, max_num_groups=None, max_seq_len=None, layout="grouped", numericalize=None):
@@ -440,3 +453,103 @@ def numericalize(args, commands, n=256):
     mask = CMD_ARGS_MASK.to(args.device)[cmd].bool() & (cmd <= C_ID).unsqueeze(-1)
     rounded = args.clamp(0, n - 1) if not args.is_floating_point() else args.round().clamp(0, n - 1)
     return torch.where(mask, rounded, args)
+
+
+def _fill_inputs(name, commands, args, samples, n):
+    """the argument checks `overlap` and `compute_filling` share -> (commands [N, G, S], args [N, G, S, 11]) as the kernels
+    read them: detached, float32 or int64, contiguous"""
+    if commands.dim() not in (2, 3) or args.dim() != commands.dim() + 1 or args.shape[:-1] != commands.shape \
+            or args.shape[-1] != 11:
+        raise ValueError(f"{name}: commands (N, G, S) with args (N, G, S, 11), or (N, S) with (N, S, 11); got "
+                         f"{tuple(commands.shape)} and {tuple(args.shape)}")
+    if commands.dim() == 2:
+        commands, args = commands.unsqueeze(1), args.unsqueeze(1)
+    N, G, S = commands.shape
+    if N < 1:
+        raise ValueError(f"{name}: an empty batch")
+    if G < 1 or G > MAX_FILL_GROUPS:
+        raise ValueError(f"{name}: {G} groups per icon, at least 1 and at most {MAX_FILL_GROUPS}")
+    if S < 1 or G * S > MAX_ROWS:
+        raise ValueError(f"{name}: {G} x {S} = {G * S} rows per icon, at least 1 and at most {MAX_ROWS}")
+    if isinstance(samples, bool) or not isinstance(samples, int) or not MIN_SAMPLES <= samples <= MAX_SAMPLES:
+        raise ValueError(f"{name}: samples is an int within {MIN_SAMPLES}..{MAX_SAMPLES}; got {samples!r}")
+    if isinstance(n, bool) or not isinstance(n, int) or not 2 <= n <= 64:
+        raise ValueError(f"{name}: n is an int within 2..64; got {n!r}")
+    commands, args = commands.detach(), args.detach()
+    if commands.dtype != args.dtype or commands.dtype not in (torch.float32, torch.int64):
+        commands, args = commands.float(), args.float()
+    return commands.contiguous(), args.contiguous()
+
+
+def _overlap_counts(commands, args, samples, n, evenodd):
+    N, G, S = commands.shape
+    modes = torch.ones(N, G, dtype=torch.int32, device=commands.device)      # FILL: every sub-path gets its closing chord
+    segs, seg_counts, layer_first = ops.raster_segments_layers(commands.view(N * G, S), args.view(N * G, S, 11), modes, n=n,
+                                                               groups=G)
+    return ops.overlap_counts(segs, seg_counts, layer_first, samples=samples, evenodd=evenodd)
+
+
+def overlap(commands, args, samples=128, n=10, evenodd=False):
+    """How much of every group of an icon lies inside every other one, measured on samples x samples points: the pixel
+    centres of `render.rasterize(size=samples)`.  commands (N, G, S) with args (N, G, S, 11), or (N, S) with (N, S, 11) read
+    as G = 1; G <= 32, G * S <= 2048, 8 <= samples <= 1024, 2 <= n <= 64 points per command.  float32 and int64 are read as
+    they are, anything else as float32.  Inputs are detached; there is no gradient.  Every sub-path is closed by a chord, as
+    the rasteriser fills it; a point is inside a group when its winding number with respect to that group's chords alone is
+    not 0 (odd with evenodd=True, as `render.draw` has it).  Two launches, nothing is read back.  -> a dict:
+      "area" int32 (N, G): the points inside each group; "inter" int32 (N, G, G): the points inside both groups, symmetric,
+      with "area" on its diagonal; "fraction" float32 (N, G, G): inter[i, j] / area[i], the share of group i that lies inside
+      group j, 0 where area[i] is 0.
+    This is the package's own overlap measure, in place of the reference's shapely polygons (``overlap_graph``,
+    svglib/svg_primitive.py:422-441).  Arcs draw nothing, as everywhere in the rasteriser."""
+    commands, args = _fill_inputs("overlap", commands, args, samples, n)
+    area, inter = _overlap_counts(commands, args, samples, n, bool(evenodd))
+    a = area.unsqueeze(-1)
+    fraction = torch.where(a > 0, inter.float() / a.clamp(min=1).float(), torch.zeros((), device=area.device))
+    return {"area": area, "inter": inter, "fraction": fraction}
+
+
+def compute_filling(commands, args, rule="evenodd", threshold=0.9, samples=128, n=10, evenodd=False, closed=None):
+    """``SVGPathGroup.compute_filling`` (svglib/svg_primitive.py:392-420) for a batch, every group of an icon taken as one of
+    the reference's sub-paths: which groups are filled, which are holes, and in what order to paint them.  Input and limits as
+    for `overlap`; `closed` is an optional bool (N, G), default all true: it stands in for the reference's ``SVGPath.closed``,
+    which tensors do not carry.  Three launches (the rasteriser's segment pass, the overlap counts, the walk); nothing is
+    read back.  No gradient.  The definition (include/dsvg.h; tests/paths_fill_ref.py restates it):
+     1. group i participates when closed[i] and area[i] > 0 (`overlap`); every other group gets filling 0, depth -1, parent
+        -1 and has no edges.
+     2. there is an edge j -> i ("j covers i") when i != j, both participate and inter[i, j] > threshold * area[i]
+        (``overlap_graph`` with this package's overlap measure; 0 < threshold <= 1).
+     3. clockwise[i] is ``SVGPath.is_clockwise`` over the drawing commands of the group, by step 5 of `canonicalize`; closing
+        chords are not part of it.
+     4. the roots are the participating groups nothing covers, in ascending index; each starts a walk at current = [(d = 1,
+        root)].  Per level, for (d, g) in current in ascending g: filling[g] = FILL (1) if d != 0 else ERASE (2), depth[g] =
+        the level; every group g2 that g covers, that is still in the graph and has not been visited in this level, is
+        visited in ascending order with parent g and d2 = 1 - d (rule="evenodd"), or d2 = d + 1 if clockwise[g2] ==
+        clockwise[g] else d - 1 (rule="orientation", the reference's).  Then current leaves the graph, and the next current
+        is the visited groups nothing covers any more.  A group that is never reached - two groups that cover each other,
+        for instance - keeps filling 0.
+     5. paint_order is the groups sorted stably by (filling 0 last, depth, index): an ERASE never precedes the FILL it cuts.
+    The reference iterates Python sets, so the order inside a level (ascending here) is the only place where the walk can
+    differ from it: when two groups of one level reach the same group with different d2.  rule="evenodd" is the default
+    because canonical icons, the ones the model emits, are all clockwise: orientation carries no information there.
+    -> a dict: "filling" int64 (N, G), as `render.draw(filling=...)` and ``PackedSVGStore.from_batch(filling=...)`` take it;
+      "depth", "parent" int32 (N, G); "clockwise" bool (N, G); "paint_order" int64 (N, G): ``torch.gather`` with it reorders
+      commands, args and filling for painting; "area", "inter" as `overlap` returns them.
+    ``SVG.group_overlapping_paths`` (the regrouping into groups of several sub-paths) is not provided: "parent" and "depth"
+    are what it needs."""
+    if rule not in ops.FILLING_RULES:
+        raise ValueError(f"compute_filling: rule 'evenodd' or 'orientation'; got {rule!r}")
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not 0 < threshold <= 1:
+        raise ValueError(f"compute_filling: threshold is a number within (0, 1]; got {threshold!r}")
+    commands, args = _fill_inputs("compute_filling", commands, args, samples, n)
+    N, G, _ = commands.shape
+    if closed is None:
+        closed = torch.ones(N, G, dtype=torch.bool, device=commands.device)
+    else:
+        if not isinstance(closed, torch.Tensor) or tuple(closed.shape) != (N, G) or closed.dtype != torch.bool:
+            raise ValueError(f"compute_filling: closed is a bool tensor of shape {(N, G)}; got "
+                             f"{tuple(closed.shape) if isinstance(closed, torch.Tensor) else closed!r}")
+        closed = closed.detach().to(commands.device).contiguous()
+    area, inter = _overlap_counts(commands, args, samples, n, bool(evenodd))
+    res = ops.filling_from_counts(area, inter, commands, args, closed, threshold=float(threshold), rule=rule)
+    res["area"], res["inter"] = area, inter
+    return res

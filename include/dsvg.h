@@ -61,7 +61,8 @@ extern "C" {
  *     Still 19: dsvg_paths_transform / dsvg_assemble_augmented added (affine step programs for a whole batch, and batch
  *     assembly over a float32 store with the augmentation applied on load), on the same terms.
  *     Still 19: dsvg_raster_segments_layers / dsvg_raster_sweep_layers added (layered RGB images: per-group outline, fill and
- *     erase, colours and opacities), on the same terms. */
+ *     erase, colours and opacities), on the same terms.
+ *     Still 19: dsvg_overlap_counts / dsvg_filling_from_counts added (filling of a decoded batch), on the same terms. */
 #define DSVG_ABI_VERSION 19
 
 const char* dsvg_last_error(void);
@@ -759,6 +760,61 @@ int dsvg_canonicalize(int32_t itype, const void* commands, const void* args, int
                       int32_t S_out, int32_t layout, int32_t numericalize, void* out_commands, void* out_args,
                       int32_t* n_groups, int32_t* len_groups, int32_t* source_group, uint8_t* reversed, uint8_t* valid,
                       void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Filling of a decoded batch (csrc/paths_fill.hip): which groups of an icon are filled, which are holes (erase
+ * paths), and in what order to paint them - SVGPathGroup.compute_filling over overlap_graph (deepsvg/svglib/svg_primitive.py:
+ * 392-441), which SVG.canonicalize_new calls on all sub-paths of an icon (svg.py:312-331).  The reference measures overlap
+ * with shapely polygons; the measure here is this package's own, on the rasteriser's chord records and crossing rule.  The
+ * result feeds the `modes` table of the layered rasteriser as it is.  tests/paths_fill_ref.py restates the definition in
+ * float64.  Arcs are out of scope, as everywhere in the rasteriser; SVG.group_overlapping_paths (the regrouping into groups
+ * of several sub-paths) is not provided: `parent` and `depth` are what it needs.
+ *  overlap_counts: segs / seg_counts / layer_first of dsvg_raster_segments_layers with every group's mode DSVG_LAYER_FILL (every
+ *    sub-path has its closing chord), cap records per icon, 1 <= G <= 32 groups, 8 <= samples = K <= 1024.  The samples are the
+ *    K x K pixel centres of an image of size K: ((col + 0.5) s, (row + 0.5) s), s = 256 / K, the fp32 expressions of
+ *    raster_sweep.  A sample is inside group i when its winding number with respect to the chords of group i alone (the
+ *    half-open rule of "Images of a decoded batch", end y taken from the next record as raster_sweep takes it; the sign test
+ *    is the sweeps' e = fmaf(dx, py, -p), p = fl(dy px), with the rounding residual of p taken out: e - fmaf(dy, px, -p), so
+ *    that a sample ON a chord, whose crossing lies at x == cx, counts nothing - in the sweeps the residual decides there,
+ *    unseen in an image, where the coverage is 0.5 on both sides) is not 0, or is odd when `evenodd` is set.  The counts may
+ *    therefore differ from the pixels a sweep calls inside by pixels whose centre is on a chord, and lie between the pixels
+ *    with ink > 0.5 and those with ink >= 0.5 of dsvg_raster_sweep.  area[b, i] int32 [B, G] += the samples inside
+ *    group i, inter[b, i, j] int32 [B, G, G] += the samples inside both i and j: symmetric, its diagonal is area.  Both tables
+ *    are ADDED to with integer atomics and must be zero on entry; integer sums do not depend on their order: bit-
+ *    reproducible.  layer_first from any producer is clamped into 0..seg_counts[b] and made non-decreasing; a group without
+ *    records counts nothing.  One workgroup per (icon, tile of 32 x 32 samples), no distance work.
+ *  filling_from_counts: area / inter as above, commands [N, G, S] / args [N, G, S, 11] of dtype `itype` (DSVG_F32 or DSVG_I64,
+ *    read as fp32 as dsvg_canonicalize reads them), G * S <= 2048, participating uint8 [N, G], 0 < threshold <= 1, rule.
+ *    1. participation: group i participates when participating[b, i] != 0 and area[b, i] > 0.  Every other group gets filling
+ *       0 (DSVG_LAYER_OUTLINE), depth -1, parent -1 and has no edges.
+ *    2. edges: j -> i ("j covers i") when i != j, both participate and (double)inter[i][j] > threshold * (double)area[i].
+ *    3. orientation: clockwise[b, i] is SVGPath.is_clockwise (svg_path.py:244-252) over the drawing rows (`l`, `c`) of the
+ *       group as the rasteriser reads them (the start point of a row is the end position of the row before it, (0, 0) on row
+ *       0), by the orientation step of dsvg_canonicalize: one command: (s.x, s.y) <= (e.x, e.y) lexicographically; any other
+ *       number: the float64 sum of s.x e.y - s.y e.x, in row order, is >= 0 (so true without commands).  Closing chords are
+ *       not part of it, as in the reference.
+ *    4. traversal (svg_primitive.py:396-418): the roots are the participating groups without an in-edge at the start, taken in
+ *       ascending index, each with its own walk that starts at current = [(d = 1, root)], level 0.  Per level, for (d, n) in
+ *       current in ASCENDING n: filling[n] = d != 0 ? DSVG_LAYER_FILL : DSVG_LAYER_ERASE, depth[n] = the level, parent[n] = the
+ *       group that visited n in the level before (-1 for a root); then every out-neighbour n2 of n that has not been
+ *       removed and has not been visited in this level, in ascending order, is visited by n with d2 = d + (clockwise[n2] ==
+ *       clockwise[n] ? 1 : -1) (DSVG_FILLING_ORIENTATION, the reference's rule) or d2 = 1 - d (DSVG_FILLING_EVENODD).  Then
+ *       current is removed from the graph, and the next current is the visited groups that are left without an in-edge.  A
+ *       group that is never reached (two groups that cover each other, for instance) keeps filling 0.  The reference
+ *       iterates Python sets, so the order inside a level is the one place where this can differ from it: when two groups of
+ *       one level reach the same group with different d2.
+ *    5. paint order: paint_order[b, :] int64 is the groups sorted stably by (filling 0 last, depth, index): an ERASE never
+ *       precedes the FILL it cuts.
+ *    filling int64 [N, G], depth / parent int32 [N, G], clockwise uint8 [N, G], paint_order int64 [N, G]: every element is
+ *    written.  One lane per icon; no atomics, nothing is read back. */
+#define DSVG_FILLING_EVENODD 0
+#define DSVG_FILLING_ORIENTATION 1
+int dsvg_overlap_counts(const void* segs, const int32_t* seg_counts, const int32_t* layer_first, int64_t B, int64_t cap,
+                        int32_t G, int32_t samples, int32_t evenodd, int32_t* area, int32_t* inter, void* stream);
+int dsvg_filling_from_counts(int32_t itype, const int32_t* area, const int32_t* inter, const void* commands, const void* args,
+                             const uint8_t* participating, int64_t N, int32_t G, int32_t S, double threshold, int32_t rule,
+                             int64_t* filling, int32_t* depth, int32_t* parent, uint8_t* clockwise, int64_t* paint_order,
+                             void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Commands split and arcs converted, for a whole batch (csrc/paths_expand.hip): SVGPath.split (deepsvg/svglib/svg_path.py:
