@@ -27,6 +27,15 @@
 //   dsvg_raster_segments_bwd  the transpose of dsvg_raster_segments (linear in args): one workgroup per image, the forward's two
 //                             scans, one thread per token gathers its own command's chords, the next row's (whose start point
 //                             is this row's end position) and the closing chords that start or end at it, in float64.
+// The gradient of a layered image (a layer's coverage depends on the chords through the distance to the nearest chord of ITS group):
+//   dsvg_raster_sweep_layers_nn      dsvg_raster_sweep_layers' kernel with one more template flag: every fold also stores the
+//                                    layer's clamped coverage and the record index of its nearest chord (-1 where saturated).
+//   dsvg_raster_blend_bwd            one workgroup per image, a lane per pixel: a forward walk over the layers rebuilds the canvas
+//                                    and leaves sum_c dout_c (p_c - C_{g-1,c}) in the dcov slot, a reverse walk carries T = prod (1 -
+//                                    alpha) and finishes the slot; d colour and d opacity through a shuffle tree per wave into LDS
+//                                    accumulators of the wave's own, summed in wave order.  No atomics, bit-reproducible.
+//   dsvg_raster_sweep_layers_bwd     dsvg_raster_sweep_bwd's walk with the layer of a record found from the layer table.
+//   dsvg_raster_segments_layers_bwd  dsvg_raster_segments_bwd's kernel under a template flag: closing chords by the group's mode.
 #include <type_traits>
 
 #include "dsvg_common.h"
@@ -286,11 +295,15 @@ __global__ __launch_bounds__(RS_THREADS) void raster_sweep_kernel(const float* _
 constexpr int RL_MODE_SHIFT = 28;          // above every record offset (cap < 2^26)
 constexpr int RL_ENTRY_BYTES = 20;
 
-template <bool CULL>
+// NN (dsvg_raster_sweep_layers_nn): the minimum keeps the index of the record that set it, as raster_sweep_kernel's NN, and
+// every fold also stores the layer's clamped coverage and that index (where 0 < cov < 1, -1 elsewhere) at [b, g]; a layer
+// the walk passes over gets 0 and -1.  `cov` and `idx` are not touched without NN.
+template <bool CULL, bool NN>
 __global__ __launch_bounds__(RS_THREADS) void raster_sweep_layers_kernel(
     const float* __restrict__ segs, const int32_t* __restrict__ seg_counts, const int32_t* __restrict__ layer_first,
     const int32_t* __restrict__ modes, const float* __restrict__ paint, long long cap, int G, int NL, int size, int tiles, float s,
-    float half_w, int compound_mode, int evenodd, float bg0, float bg1, float bg2, float* __restrict__ out) {
+    float half_w, int compound_mode, int evenodd, float bg0, float bg1, float bg2, float* __restrict__ out,
+    float* __restrict__ cov_out, int32_t* __restrict__ idx_out) {
     __shared__ __attribute__((aligned(16))) float4 rec[RS_CHORDS * 2];
     __shared__ __attribute__((aligned(16))) float4 box[CULL ? RS_CHORDS : 1];
     extern __shared__ __attribute__((aligned(16))) float4 lpaint[];
@@ -305,14 +318,31 @@ __global__ __launch_bounds__(RS_THREADS) void raster_sweep_layers_kernel(
     const int col = col0 + (lane & 15), row = row0 + (lane >> 4);
     const float cx = ((float)col + 0.5f) * s;
     float cy[RS_PIX], m[RS_PIX], cv0[RS_PIX], cv1[RS_PIX], cv2[RS_PIX];
-    int wind[RS_PIX];
+    int wind[RS_PIX], mi[RS_PIX];
 #pragma unroll
     for (int r = 0; r < RS_PIX; ++r) {
         cy[r] = ((float)(row + 4 * r) + 0.5f) * s;
         m[r] = INFINITY;
         wind[r] = 0;
         cv0[r] = bg0; cv1[r] = bg1; cv2[r] = bg2;
+        if constexpr (NN) mi[r] = -1;
     }
+    // NN: what layer gl keeps of the lane's pixel r (lanes past the image edge keep nothing)
+    auto keep = [&](int gl, int r, float cov, int nearest) {
+        if constexpr (NN) {
+            if (col < size && row + 4 * r < size) {
+                const long long o = ((b * NL + gl) * size + (row + 4 * r)) * size + col;
+                cov_out[o] = cov;
+                idx_out[o] = nearest;
+            }
+        }
+    };
+    auto pass_over = [&](int gl) {            // a layer without records
+        if constexpr (NN) {
+#pragma unroll
+            for (int r = 0; r < RS_PIX; ++r) keep(gl, r, 0.f, -1);
+        }
+    };
     const float qx0 = ((float)col0 + 0.5f) * s, qx1 = ((float)(col0 + RS_QUAD - 1) + 0.5f) * s;
     const float qy0 = ((float)row0 + 0.5f) * s, qy1 = ((float)(row0 + RS_QUAD - 1) + 0.5f) * s;
     // the culling reach of raster_sweep_kernel, per layer mode
@@ -337,7 +367,10 @@ __global__ __launch_bounds__(RS_THREADS) void raster_sweep_layers_kernel(
         return __builtin_amdgcn_readfirstlane(g + 1 < NL ? lfirst[g + 1] & ((1 << RL_MODE_SHIFT) - 1) : cnt);
     };
     int g = 0;                        // the layer the next record belongs to: the first one that ends past it
-    while (g < NL && end_of(g) <= 0) ++g;
+    while (g < NL && end_of(g) <= 0) {
+        pass_over(g);
+        ++g;
+    }
 
     for (int j0 = 0; j0 < cnt; j0 += RS_CHORDS) {
         if (j0) __syncthreads();                       // the tile of the step before has been read
@@ -371,7 +404,13 @@ __global__ __launch_bounds__(RS_THREADS) void raster_sweep_layers_kernel(
                 if (near) {
                     const float t = fminf(fmaxf(fmaf(px, A.z, py * A.w) * B.x, 0.f), 1.f);
                     const float qx = fmaf(-t, A.z, px), qy = fmaf(-t, A.w, py);
-                    m[r] = fminf(m[r], fmaf(qx, qx, qy * qy));
+                    if constexpr (NN) {   // the value fminf keeps and who set it, as raster_sweep_kernel
+                        const float d2 = fmaf(qx, qx, qy * qy);
+                        if (d2 < m[r]) {
+                            m[r] = d2;
+                            mi[r] = j0 + jl;
+                        }
+                    } else m[r] = fminf(m[r], fmaf(qx, qx, qy * qy));
                 }
             }
         };
@@ -427,9 +466,16 @@ __global__ __launch_bounds__(RS_THREADS) void raster_sweep_layers_kernel(
                 cv2[r] = fmaf(alpha, p2 - cv2[r], cv2[r]);
                 m[r] = INFINITY;
                 wind[r] = 0;
+                if constexpr (NN) {
+                    keep(g, r, cov, cov > 0.f && cov < 1.f ? mi[r] : -1);
+                    mi[r] = -1;
+                }
             }
             ++g;
-            while (g < NL && end_of(g) <= le) ++g;
+            while (g < NL && end_of(g) <= le) {
+                pass_over(g);
+                ++g;
+            }
         }
     }
     if (col >= size) return;
@@ -510,9 +556,13 @@ __global__ __launch_bounds__(RB_THREADS) void raster_sweep_bwd_kernel(const floa
 // row's end position, whatever this row holds; row 0's start is the constant (0, 0)), the a of the closing chord of the
 // sub-path that ends at it and the b of the closing chord of the sub-path that starts on the row after it.  float64 sums,
 // as sample_points_bwd_kernel; records at or past seg_counts[b] read as zero.  Every element of the row is written.
+// LAYERS (dsvg_raster_segments_layers_bwd, the transpose of raster_segments_kernel<float, true>): `fill` is per group, read from
+// modes[b, g] as the forward reads it; without LAYERS `modes` is not touched.
+template <bool LAYERS>
 __global__ __launch_bounds__(SP_THREADS) void raster_segments_bwd_kernel(const float* __restrict__ commands, const float* __restrict__ dsegs,
                                                                          const int32_t* __restrict__ seg_counts, int G, int L, int n,
-                                                                         int fill, long long cap, float* __restrict__ dargs) {
+                                                                         int fill, long long cap, float* __restrict__ dargs,
+                                                                         const int32_t* __restrict__ modes) {
     __shared__ int pre[SP_MAX_TOK + 1];
     __shared__ int cl[SP_MAX_TOK + 1];
     __shared__ int last[SP_MAX_TOK];          // last token of the q-th sub-path
@@ -521,8 +571,20 @@ __global__ __launch_bounds__(SP_THREADS) void raster_segments_bwd_kernel(const f
     const int tid = threadIdx.x;
     const int T_ = G * L;
     const float* cmd = commands + b * T_;
+    // whether the sub-paths of token t's group are closed (t < T_)
+    auto closes = [&](int t) -> int {
+        if constexpr (LAYERS) {
+            const int m = modes[b * G + t / L];
+            return m == DSVG_LAYER_FILL || m == DSVG_LAYER_ERASE;
+        } else {
+            return fill;
+        }
+    };
     block_flag_scan<SP_MAX_TOK>(T_, pre, wtot, [&](int t) { return is_drawing(cmd, t, T_); });
-    block_flag_scan<SP_MAX_TOK>(T_, cl, wtot, [&](int t) { return subpath_ends(pre, t, T_, L, fill); });
+    if constexpr (LAYERS)
+        block_flag_scan<SP_MAX_TOK>(T_, cl, wtot, [&](int t) { return subpath_ends(pre, t, T_, L, t < T_ ? closes(t) : 0); });
+    else
+        block_flag_scan<SP_MAX_TOK>(T_, cl, wtot, [&](int t) { return subpath_ends(pre, t, T_, L, fill); });
     for (int t = tid; t < T_; t += SP_THREADS)
         if (cl[t + 1] > cl[t]) last[cl[t]] = t;
     __syncthreads();
@@ -573,7 +635,7 @@ __global__ __launch_bounds__(SP_THREADS) void raster_segments_bwd_kernel(const f
                 ex += w0 * vx; ey += w0 * vy;
             }
         }
-        if (fill) {
+        if (LAYERS ? closes(t) : fill) {
             if (cl[t + 1] > cl[t]) {                       // a sub-path ends here: its closing chord starts at this end position
                 const float4 c = rec((pre[t] + 1) * (n - 1) + cl[t]);
                 ex += (double)c.x; ey += (double)c.y;
@@ -590,6 +652,185 @@ __global__ __launch_bounds__(SP_THREADS) void raster_segments_bwd_kernel(const f
         row[5] = (float)c1x; row[6] = (float)c1y; row[7] = (float)c2x; row[8] = (float)c2y;
         row[9] = (float)ex; row[10] = (float)ey;
     }
+}
+
+// The gradient of a layered image (include/dsvg.h, "Layered images: the gradient").
+// The record at which layer g ends, as raster_sweep_layers_kernel clamps it
+__device__ __forceinline__ int layer_end(const int32_t* __restrict__ layer_first, long long b, int G, int NL, int g, int cnt,
+                                         int compound_mode) {
+    return g + 1 < NL && compound_mode < 0 ? min(max(layer_first[b * (G + 1) + g + 1], 0), cnt) : cnt;
+}
+
+__device__ __forceinline__ int layer_mode(const int32_t* __restrict__ modes, long long b, int G, int g, int compound_mode) {
+    if (compound_mode >= 0) return compound_mode;
+    const int mode = modes[b * G + g];
+    return mode == DSVG_LAYER_FILL || mode == DSVG_LAYER_ERASE ? mode : DSVG_LAYER_OUTLINE;
+}
+
+constexpr int BB_LIVE = 4;                 // bit of a layer word next to its mode (0..2): the layer has records
+
+// The backward of the blend chain.  One workgroup of 1, 2 or 4 waves per image, one lane per pixel, 64 pixels of a wave at a
+// time.  A layer has records exactly when its end lies past every end before it (the forward's walk passes over the
+// others).  Forward walk over the layers that have records: the canvas by the forward's fmaf chain, and sum_c dout_c
+// (p_c - C_{g-1,c}) left in the layer's dcov slot; reverse walk with T = prod_{k > g} (1 - alpha_k): d alpha = T * slot,
+// dcov = d alpha * opacity, and the pixel's terms of d opacity (d alpha * cov) and d colour (T alpha dout_c; none on an ERASE
+// layer) reduced over the wave by a fixed-shape __shfl_xor tree and added to the wave's own LDS accumulator of the layer by
+// lane 0: a fixed order, no atomics.  The waves' accumulators are summed in wave order at the end; an element of paint
+// outside 0..1 (the forward clamped it) or NaN gets 0.  LDS (dynamic): waves * NL float4, then 2 NL ints.
+__global__ __launch_bounds__(256) void raster_blend_bwd_kernel(
+    const float* __restrict__ cov, const int32_t* __restrict__ seg_counts, const int32_t* __restrict__ layer_first,
+    const int32_t* __restrict__ modes, const float* __restrict__ paint, const float* __restrict__ dout, long long cap, int G,
+    int NL, int size, int compound_mode, float bg0, float bg1, float bg2, float* __restrict__ dcov, float* __restrict__ dpaint) {
+    extern __shared__ __attribute__((aligned(16))) float4 acc[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = (int)blockDim.x >> 6;
+    int* lend = reinterpret_cast<int*>(acc + nw * NL);
+    int* lword = lend + NL;
+    const long long b = blockIdx.x;
+    const int cnt = chamfer_count(seg_counts, b, cap);
+    const long long plane = (long long)size * size;
+    for (int i = tid; i < nw * NL; i += (int)blockDim.x) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int g = tid; g < NL; g += (int)blockDim.x) lend[g] = layer_end(layer_first, b, G, NL, g, cnt, compound_mode);
+    __syncthreads();
+    for (int g = tid; g < NL; g += (int)blockDim.x) {
+        int before = 0;
+        for (int k = 0; k < g; ++k) before = max(before, lend[k]);
+        lword[g] = lend[g] > before ? layer_mode(modes, b, G, g, compound_mode) | BB_LIVE : 0;
+    }
+    __syncthreads();
+    const float* cb = cov + b * NL * plane;
+    float* db = dcov + b * NL * plane;
+    const float* gb = dout + b * 3 * plane;
+    const float* pb = paint + b * G * 4;
+    auto unit = [](float v) { return fminf(fmaxf(v, 0.f), 1.f); };
+    for (long long base = (long long)wave * 64; base < plane; base += blockDim.x) {          // wave-uniform
+        const long long pix = base + lane;
+        const bool on = pix < plane;
+        float g0 = 0.f, g1 = 0.f, g2 = 0.f;
+        if (on) {
+            g0 = gb[pix]; g1 = gb[plane + pix]; g2 = gb[2 * plane + pix];
+        }
+        float c0 = bg0, c1 = bg1, c2 = bg2;
+        for (int g = 0; g < NL; ++g) {
+            const int word = __builtin_amdgcn_readfirstlane(lword[g]);
+            if (!(word & BB_LIVE)) {
+                if (on) db[g * plane + pix] = 0.f;
+                continue;
+            }
+            const bool erase = (word & 3) == DSVG_LAYER_ERASE;
+            const float* p = pb + g * 4;
+            const float opacity = unit(p[3]);
+            const float p0 = erase ? bg0 : unit(p[0]), p1 = erase ? bg1 : unit(p[1]), p2 = erase ? bg2 : unit(p[2]);
+            if (on) {
+                const float alpha = opacity * cb[g * plane + pix];
+                const float e0 = p0 - c0, e1 = p1 - c1, e2 = p2 - c2;
+                db[g * plane + pix] = fmaf(g2, e2, fmaf(g1, e1, g0 * e0));
+                c0 = fmaf(alpha, e0, c0); c1 = fmaf(alpha, e1, c1); c2 = fmaf(alpha, e2, c2);
+            }
+        }
+        float T = 1.f;
+        for (int g = NL - 1; g >= 0; --g) {
+            const int word = __builtin_amdgcn_readfirstlane(lword[g]);
+            if (!(word & BB_LIVE)) continue;
+            const bool erase = (word & 3) == DSVG_LAYER_ERASE;
+            const float opacity = unit(pb[g * 4 + 3]);
+            float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+            if (on) {
+                const float cv = cb[g * plane + pix];
+                const float alpha = opacity * cv;
+                const float dalpha = T * db[g * plane + pix];
+                db[g * plane + pix] = dalpha * opacity;
+                s3 = dalpha * cv;
+                if (!erase) {
+                    const float ta = T * alpha;
+                    s0 = ta * g0; s1 = ta * g1; s2 = ta * g2;
+                }
+                T = fmaf(-alpha, T, T);
+            }
+#pragma unroll
+            for (int o = 32; o; o >>= 1) {
+                s0 += __shfl_xor(s0, o, 64); s1 += __shfl_xor(s1, o, 64);
+                s2 += __shfl_xor(s2, o, 64); s3 += __shfl_xor(s3, o, 64);
+            }
+            if (lane == 0) {
+                float4 v = acc[wave * NL + g];
+                v.x += s0; v.y += s1; v.z += s2; v.w += s3;
+                acc[wave * NL + g] = v;
+            }
+        }
+    }
+    __syncthreads();
+    for (int g = tid; g < G; g += (int)blockDim.x) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (g < NL)
+            for (int w = 0; w < nw; ++w) {
+                const float4 a = acc[w * NL + g];
+                v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
+            }
+        const float* p = pb + g * 4;
+        auto given = [](float x, float d) { return x >= 0.f && x <= 1.f ? d : 0.f; };
+        reinterpret_cast<float4*>(dpaint)[b * G + g] = make_float4(given(p[0], v.x), given(p[1], v.y), given(p[2], v.z), given(p[3], v.w));
+    }
+}
+
+// raster_sweep_bwd_kernel for a layered image: the layer of record j is the first one that ends past j (the forward's walk),
+// its mode decides the sign rule and the reach, and cov, idx and dcov are read at [b, g].
+template <int GW>
+__global__ __launch_bounds__(RB_THREADS) void raster_sweep_layers_bwd_kernel(
+    const float* __restrict__ segs, const int32_t* __restrict__ seg_counts, const int32_t* __restrict__ layer_first,
+    const int32_t* __restrict__ modes, const float* __restrict__ cov, const int32_t* __restrict__ idx, const float* __restrict__ dcov,
+    long long cap, int G, int NL, int size, int blocks_per_image, float s, float reach_line, float reach_fill, int compound_mode,
+    float* __restrict__ dsegs) {
+    constexpr int PER = RB_THREADS / GW;                  // chords of a workgroup
+    const long long b = blockIdx.x / blocks_per_image;
+    const int j = (int)(blockIdx.x % blocks_per_image) * PER + (int)threadIdx.x / GW;
+    const int l = (int)threadIdx.x % GW;
+    const int cnt = chamfer_count(seg_counts, b, cap);
+    if (j >= cnt) return;                                 // whole groups leave: the shuffles below stay inside a group
+    // a linear search, up to NL dependent loads per record, by every lane of the group: sized for the G of the data sets (8, at
+    // most a few dozen), not for the 2048 the table may hold.  The ends of a foreign table need not be monotone, so a binary
+    // search would not find the forward's layer; a running maximum of the ends in LDS would allow one
+    int g = 0;
+    while (g + 1 < NL && layer_end(layer_first, b, G, NL, g, cnt, compound_mode) <= j) ++g;
+    const bool fill = layer_mode(modes, b, G, g, compound_mode) != DSVG_LAYER_OUTLINE;
+    const float reach = fill ? reach_fill : reach_line;
+    const float* r = segs + (b * cap + j) * RS_REC;
+    const float ax = r[0], ay = r[1], dx = r[2], dy = r[3];
+    const float len2 = fmaf(dx, dx, dy * dy);
+    const float inv = len2 > 1e-30f ? 1.f / len2 : 0.f;
+    const float fsize = (float)size;
+    auto first = [&](float v) { return (int)fminf(fmaxf(floorf((v - reach) / s - 0.5f), 0.f), fsize); };
+    auto end = [&](float v) { return (int)fminf(fmaxf(ceilf((v + reach) / s - 0.5f) + 1.f, 0.f), fsize); };
+    const int c0 = first(fminf(ax, ax + dx)), c1 = end(fmaxf(ax, ax + dx));
+    const int r0 = first(fminf(ay, ay + dy)), r1 = end(fmaxf(ay, ay + dy));
+    const int w = c1 - c0, np = w > 0 && r1 > r0 ? w * (r1 - r0) : 0;          // <= 4096^2
+    const long long layer = (b * NL + g) * size * size;
+    const float* ob = cov + layer;
+    const int32_t* ib = idx + layer;
+    const float* gb = dcov + layer;
+    float sax = 0.f, say = 0.f, sbx = 0.f, sby = 0.f;
+    for (int p = l; p < np; p += GW) {
+        const int pr = p / w;
+        const int row = r0 + pr, col = c0 + (p - pr * w);
+        const long long pix = (long long)row * size + col;
+        if (ib[pix] != j) continue;
+        const float ink = ob[pix];
+        if (!(ink > 0.f && ink < 1.f)) continue;
+        const float px = ((float)col + 0.5f) * s - ax, py = ((float)row + 0.5f) * s - ay;
+        const float t = fminf(fmaxf(fmaf(px, dx, py * dy) * inv, 0.f), 1.f);
+        const float qx = fmaf(-t, dx, px), qy = fmaf(-t, dy, py);
+        const float d2 = fmaf(qx, qx, qy * qy);
+        if (!(d2 > 0.f)) continue;
+        const float gd = (fill && ink > 0.5f ? gb[pix] : -gb[pix]) / (s * sqrtf(d2));          // dL/dd / d
+        const float gx = gd * qx, gy = gd * qy;
+        sax = fmaf(t - 1.f, gx, sax); say = fmaf(t - 1.f, gy, say);
+        sbx = fmaf(-t, gx, sbx); sby = fmaf(-t, gy, sby);
+    }
+#pragma unroll
+    for (int o = GW / 2; o; o >>= 1) {
+        sax += __shfl_xor(sax, o, GW); say += __shfl_xor(say, o, GW);
+        sbx += __shfl_xor(sbx, o, GW); sby += __shfl_xor(sby, o, GW);
+    }
+    if (l == 0) reinterpret_cast<float4*>(dsegs)[b * cap + j] = make_float4(sax, say, sbx, sby);
 }
 }  // namespace
 
@@ -696,34 +937,118 @@ extern "C" int dsvg_raster_sweep_nn(const void* segs, const int32_t* seg_counts,
     return sweep_launch("raster_sweep_nn", segs, seg_counts, B, cap, size, stroke_width, flags, out, idx, true, stream);
 }
 
-extern "C" int dsvg_raster_sweep_layers(const void* segs, const int32_t* seg_counts, const int32_t* layer_first,
-                                        const int32_t* modes, const float* paint, const float* background, int64_t B,
-                                        int64_t cap, int32_t G, int32_t size, float stroke_width, int32_t flags, float* out,
-                                        void* stream) {
+namespace {
+// what the layered entry points take a `flags` word for, and the tables a layered (not compound) image needs
+constexpr int32_t RL_FLAGS = DSVG_RASTER_CULL | DSVG_RASTER_EVENODD | DSVG_RASTER_COMPOUND;
+
+int layers_args_ok(const char* name, int32_t G, const float* background) {
+    DSVG_CHECK_ARG(G >= 1 && G <= SP_MAX_TOK, "%s: G = %d layers per image, need 1..%d", name, G, SP_MAX_TOK);
+    for (int q = 0; q < 3; ++q)
+        DSVG_CHECK_ARG(background[q] >= 0.f && background[q] <= 1.f, "%s: background[%d] = %g, need 0..1", name, q,
+                       (double)background[q]);
+    return 0;
+}
+
+int layer_compound_mode(int32_t flags) {
+    return flags & DSVG_RASTER_COMPOUND ? (flags & DSVG_RASTER_FILL ? DSVG_LAYER_FILL : DSVG_LAYER_OUTLINE) : -1;
+}
+
+// dsvg_raster_sweep_layers (cov and idx null) and dsvg_raster_sweep_layers_nn, refused under the name of the caller
+int sweep_layers_launch(const char* name, const void* segs, const int32_t* seg_counts, const int32_t* layer_first,
+                        const int32_t* modes, const float* paint, const float* background, int64_t B, int64_t cap, int32_t G,
+                        int32_t size, float stroke_width, int32_t flags, float* out, float* cov, int32_t* idx, bool nn,
+                        void* stream) {
     const int64_t tiles = (size + RS_TILE - 1) / RS_TILE;
     const bool compound = flags & DSVG_RASTER_COMPOUND;
-    if (sweep_args_ok("raster_sweep_layers", segs && seg_counts && paint && background && out && (compound || (layer_first && modes)),
-                      B, cap, size, stroke_width, flags,
-                      DSVG_RASTER_CULL | DSVG_RASTER_EVENODD | DSVG_RASTER_COMPOUND | (compound ? DSVG_RASTER_FILL : 0),
-                      tiles * tiles))
+    if (sweep_args_ok(name, segs && seg_counts && paint && background && out && (compound || (layer_first && modes)) &&
+                                (!nn || (cov && idx)),
+                      B, cap, size, stroke_width, flags, RL_FLAGS | (compound ? DSVG_RASTER_FILL : 0), tiles * tiles))
         return -1;
-    DSVG_CHECK_ARG(G >= 1 && G <= SP_MAX_TOK, "raster_sweep_layers: G = %d layers per image, need 1..%d", G, SP_MAX_TOK);
-    for (int q = 0; q < 3; ++q)
-        DSVG_CHECK_ARG(background[q] >= 0.f && background[q] <= 1.f, "raster_sweep_layers: background[%d] = %g, need 0..1", q,
-                       (double)background[q]);
+    if (layers_args_ok(name, G, background)) return -1;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)(B * tiles * tiles)), block(RS_THREADS);
     const float s = 256.f / (float)size, half_w = 0.5f * stroke_width;
     const int NL = compound ? 1 : G;
-    const int compound_mode = compound ? (flags & DSVG_RASTER_FILL ? DSVG_LAYER_FILL : DSVG_LAYER_OUTLINE) : -1;
-#define RL_LAUNCH(C)                                                                                                          \
-    hipLaunchKernelGGL((raster_sweep_layers_kernel<C>), grid, block, (size_t)NL * RL_ENTRY_BYTES, st, (const float*)segs,      \
+    const int compound_mode = layer_compound_mode(flags);
+#define RL_LAUNCH(C, N)                                                                                                       \
+    hipLaunchKernelGGL((raster_sweep_layers_kernel<C, N>), grid, block, (size_t)NL * RL_ENTRY_BYTES, st, (const float*)segs,   \
                        seg_counts, layer_first, modes, paint, (long long)cap, G, NL, size, (int)tiles, s, half_w, compound_mode, \
-                       flags & DSVG_RASTER_EVENODD ? 1 : 0, background[0], background[1], background[2], out)
-    if (flags & DSVG_RASTER_CULL) RL_LAUNCH(true);
-    else RL_LAUNCH(false);
+                       flags & DSVG_RASTER_EVENODD ? 1 : 0, background[0], background[1], background[2], out, cov, idx)
+    if (nn) {
+        if (flags & DSVG_RASTER_CULL) RL_LAUNCH(true, true);
+        else RL_LAUNCH(false, true);
+    } else {
+        if (flags & DSVG_RASTER_CULL) RL_LAUNCH(true, false);
+        else RL_LAUNCH(false, false);
+    }
 #undef RL_LAUNCH
-    DSVG_LAUNCH_CHECK("raster_sweep_layers");
+    DSVG_LAUNCH_CHECK(name);
+    return 0;
+}
+}  // namespace
+
+extern "C" int dsvg_raster_sweep_layers(const void* segs, const int32_t* seg_counts, const int32_t* layer_first,
+                                        const int32_t* modes, const float* paint, const float* background, int64_t B,
+                                        int64_t cap, int32_t G, int32_t size, float stroke_width, int32_t flags, float* out,
+                                        void* stream) {
+    return sweep_layers_launch("raster_sweep_layers", segs, seg_counts, layer_first, modes, paint, background, B, cap, G, size,
+                               stroke_width, flags, out, nullptr, nullptr, false, stream);
+}
+
+extern "C" int dsvg_raster_sweep_layers_nn(const void* segs, const int32_t* seg_counts, const int32_t* layer_first,
+                                           const int32_t* modes, const float* paint, const float* background, int64_t B,
+                                           int64_t cap, int32_t G, int32_t size, float stroke_width, int32_t flags, float* out,
+                                           float* cov, int32_t* idx, void* stream) {
+    return sweep_layers_launch("raster_sweep_layers_nn", segs, seg_counts, layer_first, modes, paint, background, B, cap, G, size,
+                               stroke_width, flags, out, cov, idx, true, stream);
+}
+
+extern "C" int dsvg_raster_blend_bwd(const float* cov, const int32_t* seg_counts, const int32_t* layer_first, const int32_t* modes,
+                                     const float* paint, const float* background, const float* dout, int64_t B, int64_t cap,
+                                     int32_t G, int32_t size, int32_t flags, float* dcov, float* dpaint, void* stream) {
+    const bool compound = flags & DSVG_RASTER_COMPOUND;
+    if (sweep_args_ok("raster_blend_bwd", cov && seg_counts && paint && background && dout && dcov && dpaint &&
+                                              (compound || (layer_first && modes)),
+                      B, cap, size, 0.f, flags, RL_FLAGS | (compound ? DSVG_RASTER_FILL : 0), 1))
+        return -1;
+    if (layers_args_ok("raster_blend_bwd", G, background)) return -1;
+    DSVG_CHECK_ARG(((uintptr_t)dpaint & 15) == 0, "raster_blend_bwd: dpaint must be 16-byte aligned");
+    const int NL = compound ? 1 : G;
+    // as many waves as have their accumulators in 64 KiB of LDS next to the layer words: 4 up to 910 layers, 1 at 2048
+    int waves = 4;
+    while (waves > 1 && (size_t)NL * (16 * waves + 8) > 65536) waves >>= 1;
+    hipLaunchKernelGGL(raster_blend_bwd_kernel, dim3((unsigned)B), dim3(64 * waves), (size_t)NL * (16 * waves + 8),
+                       (hipStream_t)stream, cov, seg_counts, layer_first, modes, paint, dout, (long long)cap, G, NL, size,
+                       layer_compound_mode(flags), background[0], background[1], background[2], dcov, dpaint);
+    DSVG_LAUNCH_CHECK("raster_blend_bwd");
+    return 0;
+}
+
+extern "C" int dsvg_raster_sweep_layers_bwd(const void* segs, const int32_t* seg_counts, const int32_t* layer_first,
+                                            const int32_t* modes, const float* cov, const int32_t* idx, const float* dcov,
+                                            int64_t B, int64_t cap, int32_t G, int32_t size, float stroke_width, int32_t flags,
+                                            float* dsegs, void* stream) {
+    const bool compound = flags & DSVG_RASTER_COMPOUND, wide = flags & DSVG_RASTER_WIDE;
+    const int per = RB_THREADS / (wide ? 64 : 16);
+    const int64_t bpi = (cap + per - 1) / per;
+    if (sweep_args_ok("raster_sweep_layers_bwd", segs && seg_counts && cov && idx && dcov && dsegs && (compound || (layer_first && modes)),
+                      B, cap, size, stroke_width, flags, RL_FLAGS | DSVG_RASTER_WIDE | (compound ? DSVG_RASTER_FILL : 0), bpi))
+        return -1;
+    DSVG_CHECK_ARG(G >= 1 && G <= SP_MAX_TOK, "raster_sweep_layers_bwd: G = %d layers per image, need 1..%d", G, SP_MAX_TOK);
+    DSVG_CHECK_ARG(((uintptr_t)dsegs & 15) == 0, "raster_sweep_layers_bwd: dsegs must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)(B * bpi)), block(RB_THREADS);
+    const float s = 256.f / (float)size;
+    // as raster_sweep_layers_kernel culls, per layer mode
+    const float reach_fill = (0.5f * s) * 1.001f + 0.01f, reach_line = (0.5f * stroke_width + 0.5f * s) * 1.001f + 0.01f;
+#define RB_LAUNCH(W)                                                                                                          \
+    hipLaunchKernelGGL((raster_sweep_layers_bwd_kernel<W>), grid, block, 0, st, (const float*)segs, seg_counts, layer_first,   \
+                       modes, cov, idx, dcov, (long long)cap, G, compound ? 1 : G, size, (int)bpi, s, reach_line, reach_fill,  \
+                       layer_compound_mode(flags), dsegs)
+    if (wide) RB_LAUNCH(64);
+    else RB_LAUNCH(16);
+#undef RB_LAUNCH
+    DSVG_LAUNCH_CHECK("raster_sweep_layers_bwd");
     return 0;
 }
 
@@ -758,8 +1083,21 @@ extern "C" int dsvg_raster_segments_bwd(const float* commands, const float* dseg
     DSVG_CHECK_ARG(commands && dsegs && seg_counts && dargs, "raster_segments_bwd: null pointer");
     if (sequence_args_ok("raster_segments_bwd", "image", B, G, L, n)) return -1;
     DSVG_CHECK_ARG(((uintptr_t)dsegs & 15) == 0, "raster_segments_bwd: dsegs must be 16-byte aligned");
-    hipLaunchKernelGGL(raster_segments_bwd_kernel, dim3((unsigned)B), dim3(SP_THREADS), 0, (hipStream_t)stream, commands, dsegs,
-                       seg_counts, G, L, n, fill ? 1 : 0, (long long)raster_cap(G, L, n, fill), dargs);
+    hipLaunchKernelGGL(raster_segments_bwd_kernel<false>, dim3((unsigned)B), dim3(SP_THREADS), 0, (hipStream_t)stream, commands,
+                       dsegs, seg_counts, G, L, n, fill ? 1 : 0, (long long)raster_cap(G, L, n, fill), dargs,
+                       (const int32_t*)nullptr);
     DSVG_LAUNCH_CHECK("raster_segments_bwd");
+    return 0;
+}
+
+extern "C" int dsvg_raster_segments_layers_bwd(const float* commands, const float* dsegs, const int32_t* seg_counts,
+                                               const int32_t* modes, int64_t B, int32_t G, int32_t L, int32_t n, float* dargs,
+                                               void* stream) {
+    DSVG_CHECK_ARG(commands && dsegs && seg_counts && modes && dargs, "raster_segments_layers_bwd: null pointer");
+    if (sequence_args_ok("raster_segments_layers_bwd", "image", B, G, L, n)) return -1;
+    DSVG_CHECK_ARG(((uintptr_t)dsegs & 15) == 0, "raster_segments_layers_bwd: dsegs must be 16-byte aligned");
+    hipLaunchKernelGGL(raster_segments_bwd_kernel<true>, dim3((unsigned)B), dim3(SP_THREADS), 0, (hipStream_t)stream, commands,
+                       dsegs, seg_counts, G, L, n, 1, (long long)raster_cap(G, L, n, 1), dargs, modes);
+    DSVG_LAUNCH_CHECK("raster_segments_layers_bwd");
     return 0;
 }

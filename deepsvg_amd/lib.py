@@ -183,6 +183,10 @@ SIGNATURES = {
     "dsvg_raster_segments_bwd": (c_i32, [vp, vp, vp, c_i64, c_i32, c_i32, c_i32, c_i32, vp, vp]),
     "dsvg_raster_segments_layers": (c_i32, [c_i32, vp, vp, c_i64, c_i32, c_i32, c_i32, vp, vp, c_i64, vp, vp, vp]),
     "dsvg_raster_sweep_layers": (c_i32, [vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_i32, vp, vp]),
+    "dsvg_raster_sweep_layers_nn": (c_i32, [vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_i32, vp, vp, vp, vp]),
+    "dsvg_raster_blend_bwd": (c_i32, [vp, vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i32, c_i32, c_i32, vp, vp, vp]),
+    "dsvg_raster_sweep_layers_bwd": (c_i32, [vp, vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_i32, vp, vp]),
+    "dsvg_raster_segments_layers_bwd": (c_i32, [vp, vp, vp, vp, c_i64, c_i32, c_i32, c_i32, vp, vp]),
     "dsvg_canonicalize": (c_i32, [c_i32, vp, vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dsvg_overlap_counts": (c_i32, [vp, vp, vp, c_i64, c_i64, c_i32, c_i32, c_i32, vp, vp, vp]),
     "dsvg_filling_from_counts": (c_i32, [c_i32, vp, vp, vp, vp, vp, c_i64, c_i32, c_i32, C.c_double, c_i32, vp, vp, vp, vp, vp, vp]),

@@ -1509,6 +1509,138 @@ def raster_segments_bwd(commands, dsegs, seg_counts, n=10, groups=1, fill=False)
     return dargs
 
 
+def _layer_call(name, segs_like, B, paint, layer_first, modes, compound, evenodd=False):
+    """the tables and the flags word the layered gradient entry points share with raster_sweep_layers -> (groups, flags)"""
+    assert compound in (None, "stroke", "fill"), f"{name}: compound {compound!r}"
+    _chk(paint)
+    assert paint.dim() == 3, f"{name}: paint [B, groups, 4]; got {list(paint.shape)}"
+    groups = paint.shape[1]
+    _chk_layer_tables(name, B, groups, segs_like.device, paint=paint)
+    if compound is None:
+        _chk(layer_first, modes)
+        _chk_layer_tables(name, B, groups, segs_like.device, layer_first=layer_first, modes=modes)
+    else:
+        assert layer_first is None and modes is None, f"{name}: a compound image has no layer tables"
+    flags = (_l.DSVG_RASTER_FILL if compound == "fill" else 0) | (_l.DSVG_RASTER_EVENODD if evenodd else 0)
+    return groups, flags | (_l.DSVG_RASTER_COMPOUND if compound else 0)
+
+
+def _background(background):
+    return C.cast((C.c_float * 3)(*[float(v) for v in background]), C.c_void_p)
+
+
+def raster_sweep_layers_nn(segs, seg_counts, layer_first, modes, paint, background=(1.0, 1.0, 1.0), size=64, stroke_width=3.2,
+                           evenodd=False, compound=None, cull=None):
+    """raster_sweep_layers that also returns what the backward needs -> (out f32 [B, 3, size, size] with raster_sweep_layers'
+    bits, cov f32 [B, NL, size, size]: the clamped coverage of every layer, 0 for a layer without chords, idx int32 [B, NL,
+    size, size]: the image-wide record index of the layer's nearest chord where 0 < cov < 1, -1 everywhere else); NL =
+    groups, or 1 with `compound`; cov and idx are the same with and without `cull`"""
+    B, cap = _chk_records(segs, seg_counts)
+    groups, flags = _layer_call("raster_sweep_layers_nn", segs, B, paint, layer_first, modes, compound, evenodd)
+    flags |= _l.DSVG_RASTER_CULL if (RASTER_CULL if cull is None else cull) else 0
+    NL, size = 1 if compound else groups, int(size)
+    out = torch.empty(B, 3, size, size, dtype=torch.float32, device=segs.device)
+    cov = torch.empty(B, NL, size, size, dtype=torch.float32, device=segs.device)
+    idx = torch.empty(B, NL, size, size, dtype=torch.int32, device=segs.device)
+    _l.check(_l.load().dsvg_raster_sweep_layers_nn(segs.data_ptr(), seg_counts.data_ptr(), _p(layer_first), _p(modes),
+                                                   paint.data_ptr(), _background(background), B, cap, groups, size,
+                                                   float(stroke_width), flags, out.data_ptr(), cov.data_ptr(), idx.data_ptr(),
+                                                   _stream()), "dsvg_raster_sweep_layers_nn")
+    return out, cov, idx
+
+
+def raster_blend_bwd(cov, seg_counts, layer_first, modes, paint, dout, cap, background=(1.0, 1.0, 1.0), compound=None):
+    """cov of raster_sweep_layers_nn, the tables and paint it was drawn with, dout f32 [B, 3, size, size] and the record
+    capacity `cap` of the image's segs -> (dcov f32 [B, NL, size, size], every element written; dpaint f32 [B, groups, 4]: the
+    gradient with respect to r, g, b, opacity summed over the pixels of each image, 0 where paint lies outside 0..1)"""
+    _chk(cov, seg_counts, dout)
+    B, NL, size = cov.shape[0], cov.shape[1], cov.shape[-1]
+    groups, flags = _layer_call("raster_blend_bwd", cov, B, paint, layer_first, modes, compound)
+    assert cov.dtype == torch.float32 and cov.shape == (B, 1 if compound else groups, size, size) and cov.is_contiguous(), \
+        f"raster_blend_bwd: cov {tuple(cov.shape)}"
+    assert dout.dtype == torch.float32 and dout.shape == (B, 3, size, size) and dout.is_contiguous(), \
+        f"raster_blend_bwd: dout {tuple(dout.shape)}"
+    assert seg_counts.dtype == torch.int32 and seg_counts.shape == (B,) and seg_counts.is_contiguous()
+    dcov = torch.empty(B, NL, size, size, dtype=torch.float32, device=cov.device)
+    dpaint = torch.empty(B, groups, 4, dtype=torch.float32, device=cov.device)
+    _l.check(_l.load().dsvg_raster_blend_bwd(cov.data_ptr(), seg_counts.data_ptr(), _p(layer_first), _p(modes), paint.data_ptr(),
+                                             _background(background), dout.data_ptr(), B, int(cap), groups, size, flags,
+                                             dcov.data_ptr(), dpaint.data_ptr(), _stream()), "dsvg_raster_blend_bwd")
+    return dcov, dpaint
+
+
+def raster_sweep_layers_bwd(segs, seg_counts, layer_first, modes, cov, idx, dcov, stroke_width=3.2, compound=None, wide=None):
+    """the records and tables, cov and idx of raster_sweep_layers_nn (same stroke_width and compound) and dcov of
+    raster_blend_bwd -> dsegs f32 [B, cap, 4] as raster_sweep_bwd returns it, each record against the pixels of its own layer"""
+    B, cap = _chk_records(segs, seg_counts)
+    assert compound in (None, "stroke", "fill"), f"raster_sweep_layers_bwd: compound {compound!r}"
+    _chk(cov, idx, dcov)
+    assert cov.dim() == 4, f"raster_sweep_layers_bwd: cov [B, layers, size, size]; got {list(cov.shape)}"
+    groups, size = (cov.shape[1], cov.shape[-1]) if compound is None else (1, cov.shape[-1])
+    if compound is None:
+        assert layer_first is not None and modes is not None, "raster_sweep_layers_bwd: layer_first and modes"
+        _chk(layer_first, modes)
+        _chk_layer_tables("raster_sweep_layers_bwd", B, groups, segs.device, layer_first=layer_first, modes=modes)
+    else:
+        assert layer_first is None and modes is None, "raster_sweep_layers_bwd: a compound image has no layer tables"
+    assert cov.dtype == torch.float32 and cov.shape == (B, groups, size, size) and cov.is_contiguous(), \
+        f"raster_sweep_layers_bwd: cov {tuple(cov.shape)}"
+    assert idx.dtype == torch.int32 and idx.shape == cov.shape and idx.is_contiguous()
+    assert dcov.dtype == torch.float32 and dcov.shape == cov.shape and dcov.is_contiguous()
+    flags = _raster_flags(compound == "fill", wide, RASTER_BWD_WIDE, _l.DSVG_RASTER_WIDE)
+    flags |= _l.DSVG_RASTER_COMPOUND if compound else 0
+    dsegs = torch.empty(B, cap, 4, dtype=torch.float32, device=segs.device)
+    _l.check(_l.load().dsvg_raster_sweep_layers_bwd(segs.data_ptr(), seg_counts.data_ptr(), _p(layer_first), _p(modes),
+                                                    cov.data_ptr(), idx.data_ptr(), dcov.data_ptr(), B, cap, groups, size,
+                                                    float(stroke_width), flags, dsegs.data_ptr(), _stream()),
+             "dsvg_raster_sweep_layers_bwd")
+    return dsegs
+
+
+def raster_segments_layers_bwd(commands, dsegs, seg_counts, modes, n=10, groups=1):
+    """raster_segments_bwd with `fill` per group: float32 commands, dsegs f32 [B, cap, 4] with the fill-mode cap, the
+    seg_counts and modes of raster_segments_layers (same n, groups) -> dargs f32 [B*groups, L, 11], every element written"""
+    _chk(commands, dsegs, seg_counts, modes)
+    B, L = _chk_sequences(commands, None, groups, "raster_segments_layers_bwd")
+    assert B >= 1
+    _chk_layer_tables("raster_segments_layers_bwd", B, groups, commands.device, modes=modes)
+    assert dsegs.dtype == torch.float32 and dsegs.shape == (B, _chord_cap(B, groups, L, n, True), 4) and dsegs.is_contiguous(), \
+        f"raster_segments_layers_bwd: dsegs {tuple(dsegs.shape)}"
+    assert seg_counts.dtype == torch.int32 and seg_counts.shape == (B,) and seg_counts.is_contiguous()
+    dargs = torch.empty(commands.shape[0], L, N_ARGS, dtype=torch.float32, device=commands.device)
+    _l.check(_l.load().dsvg_raster_segments_layers_bwd(commands.data_ptr(), dsegs.data_ptr(), seg_counts.data_ptr(),
+                                                       modes.data_ptr(), B, groups, L, int(n), dargs.data_ptr(), _stream()),
+             "dsvg_raster_segments_layers_bwd")
+    return dargs
+
+
+def draw_fwd_nn(commands, args, modes, paint, background=(1.0, 1.0, 1.0), size=64, stroke_width=3.2, evenodd=False, compound=None,
+                n=10, groups=1, cull=None):
+    """`draw` through the forward twin -> (out, (segs, seg_counts, layer_first, cov, idx)): the picture has draw's bits"""
+    if compound is None:
+        segs, seg_counts, layer_first = raster_segments_layers(commands, args, modes, n=n, groups=groups)
+    else:
+        assert modes is None, "draw_fwd_nn: a compound image has no mode table"
+        segs, seg_counts = raster_segments(commands, args, n=n, groups=groups, fill=compound == "fill")
+        layer_first = None
+    out, cov, idx = raster_sweep_layers_nn(segs, seg_counts, layer_first, modes, paint, background=background, size=size,
+                                           stroke_width=stroke_width, evenodd=evenodd, compound=compound, cull=cull)
+    return out, (segs, seg_counts, layer_first, cov, idx)
+
+
+def draw_bwd(commands, modes, paint, saved, dout, background=(1.0, 1.0, 1.0), stroke_width=3.2, compound=None, n=10, groups=1):
+    """the backward of draw_fwd_nn: raster_blend_bwd -> raster_sweep_layers_bwd -> raster_segments_layers_bwd (compound:
+    raster_segments_bwd) -> (dargs f32 [B*groups, L, 11], dpaint f32 [B, groups, 4]); float32 commands"""
+    segs, seg_counts, layer_first, cov, idx = saved
+    dcov, dpaint = raster_blend_bwd(cov, seg_counts, layer_first, modes, paint, dout, segs.shape[1], background=background,
+                                    compound=compound)
+    dsegs = raster_sweep_layers_bwd(segs, seg_counts, layer_first, modes, cov, idx, dcov, stroke_width=stroke_width,
+                                    compound=compound)
+    if compound is None:
+        return raster_segments_layers_bwd(commands, dsegs, seg_counts, modes, n=n, groups=groups), dpaint
+    return raster_segments_bwd(commands, dsegs, seg_counts, n=n, groups=groups, fill=compound == "fill"), dpaint
+
+
 # ------------------------------------------------------------------------------------------------
 # canonical path order of a batch (svglib/svg.py:333-349 on the tensors themselves; csrc/paths.hip)
 # ------------------------------------------------------------------------------------------------

@@ -19,9 +19,9 @@ data path (svglib/svg_path.py:29-32: outline, fill, erase).  Group g of an icon 
 canvas of three channels: its coverage is the stroke or fill coverage above computed from the group's OWN chords (fill rule
 non-zero or even-odd), alpha = opacity * coverage, canvas = fmaf(alpha, paint - canvas, canvas) per channel, where paint is
 the group's colour or, for an erase layer, the background - so the counter of an "O", a group of its own since
-`paths.canonicalize`, is a hole again.  ``compound=True`` draws an icon as one <path> with many sub-paths instead.  No
-gradient (`rasterize_with_grad` stays the differentiable path); the dash arrays and the point / handle / box extras of the
-reference's ``draw`` are not drawn.
+`paths.canonicalize`, is a hole again.  ``compound=True`` draws an icon as one <path> with many sub-paths instead.  `draw`
+itself carries no gradient: `draw_with_grad` draws the same bits and does (last paragraph).  The dash arrays and the point /
+handle / box extras of the reference's ``draw`` are not drawn.
 
 The gradient of an image with respect to float32 `args` (`rasterize_with_grad`, `image_loss`, `refine_to_images`; three
 more kernels of csrc/raster.hip, tests/raster_grad_ref.py restates them in float64): a pixel's ink depends on the chords only
@@ -34,14 +34,22 @@ square of INTEGRATION.md section 6 at size 64, has an exactly zero gradient); sa
 Chord vertices are linear in `args`; the start point of a command is the end position of the row before it whatever that
 row holds, and columns 0-4, padding and rows that neither draw nor precede a drawing row get exact zeros.  A gather with
 an arg-min saved by the forward: no atomics, bit-reproducible.
+
+The gradient of a layered image (`draw_with_grad`, `picture_loss`, `refine_to_pictures`; four more entry points of
+csrc/raster.hip, tests/raster_layers_grad_ref.py restates them in float64): with T_g the product of 1 - alpha_k over the layers
+above g, d out / d alpha_g = T_g (paint_g - canvas_{g-1}), d out / d paint_g = T_g alpha_g (0 for an erase layer), d alpha / d cov =
+opacity and d alpha / d opacity = cov; T is carried down from the top layer, so nothing is divided by 1 - alpha (0 inside an
+opaque fill).  A layer's coverage reaches the arguments as above, through the nearest chord among the layer's OWN chords: the
+hole of a ring pulls on its own outline.  Colours and opacities the kernel clamped get an exact 0.  The pixel sums of the paint
+gradient run in a fixed order: bit-reproducible.
 """
 import torch
 
 from . import ops
 from .metrics import _adam_refine, _evaluating, _flat_sequences
 
-__all__ = ["rasterize", "draw", "palette", "rasterize_with_grad", "image_loss", "refine_to_images", "reconstruction_images",
-           "interpolate", "interpolation_alphas"]
+__all__ = ["rasterize", "draw", "palette", "rasterize_with_grad", "image_loss", "refine_to_images", "draw_with_grad",
+           "picture_loss", "refine_to_pictures", "reconstruction_images", "interpolate", "interpolation_alphas"]
 
 
 def rasterize(commands, args, size=64, stroke_width=3.2, fill=False, n=10):
@@ -71,14 +79,14 @@ def _unit_numbers(name, what, values):
     return values
 
 
-def _per_group(name, what, value, N, G, last, device):
+def _per_group(name, what, value, N, G, last, device, keep_graph=False):
     """a table given per group ([G, *last]) or per icon and group ([N, G, *last]) -> float32, broadcastable to [N, G, *last];
-    Python lists are checked against 0..1, tensors are left to the kernel's clamp"""
+    Python lists are checked against 0..1, tensors are left to the kernel's clamp (and detached unless `keep_graph`)"""
     if not torch.is_tensor(value):
         flat = torch.tensor(value, dtype=torch.float32)
         _unit_numbers(name, what, flat.flatten().tolist())
         value = flat
-    value = value.detach().to(device=device, dtype=torch.float32)
+    value = (value if keep_graph else value.detach()).to(device=device, dtype=torch.float32)
     if tuple(value.shape) not in ((G, *last), (N, G, *last)):
         raise ValueError(f"{name}: {what} {[G, *last]} or {[N, G, *last]}; got {list(value.shape)}")
     return value
@@ -88,7 +96,7 @@ def draw(commands, args, filling=None, colors=None, opacity=1.0, background=1.0,
          fill_rule="nonzero", compound=False, n=10):
     """The groups of every icon painted one over the other into ONE RGB image, the way the reference displays an icon
     (``SVG.draw``, ``draw_colored``): commands [N, G, S] / args [N, G, S, 11] ([N, S] / [N, S, 11]: G = 1), read, detached and
-    sampled exactly as `rasterize` does -> f32 [N, 3, size, size], 1 = paper white, 0 = black.  No gradient.
+    sampled exactly as `rasterize` does -> f32 [N, 3, size, size], 1 = paper white, 0 = black.  No gradient (`draw_with_grad`).
 
     Group g is layer g; layers are painted in group order onto a canvas that starts at `background` (a number or three, in
     0..1); a group without chords is skipped.
@@ -105,8 +113,17 @@ def draw(commands, args, filling=None, colors=None, opacity=1.0, background=1.0,
     across the groups, the mode from `fill`, the paint group 0's.  With ``fill=True, fill_rule="evenodd"`` it draws the holes
     of decoded output, which carries no `filling`.  Not together with `filling`.
     A one-group black-on-white image is ``1 - rasterize(...)`` bit for bit."""
-    name = "draw"
-    commands, args, G = _flat_sequences(name, commands.detach(), args.detach())
+    commands, args, G, modes, paint, background = _draw_inputs("draw", commands, args.detach(), filling, colors, opacity,
+                                                               background, fill, fill_rule, compound)
+    return ops.draw(commands, args, modes, paint, background=background, size=size, stroke_width=stroke_width,
+                    evenodd=fill_rule == "evenodd", compound=("fill" if fill else "stroke") if compound else None, n=n, groups=G)
+
+
+def _draw_inputs(name, commands, args, filling, colors, opacity, background, fill, fill_rule, compound, keep_graph=False):
+    """the checks and tables of `draw`, under the caller's name -> (commands [N * G, S], args [N * G, S, 11], G, modes int32
+    [N, G] or None (compound), paint f32 [N, G, 4], background: three floats).  `keep_graph`: `colors` / `opacity` tensors
+    stay in the autograd graph, expanded to [N, G, ...] there (so that a per-group table sums its gradient over the icons)"""
+    commands, args, G = _flat_sequences(name, commands.detach(), args)
     N, device = commands.shape[0] // G, commands.device
     if fill_rule not in ("nonzero", "evenodd"):
         raise ValueError(f"{name}: fill_rule 'nonzero' or 'evenodd'; got {fill_rule!r}")
@@ -115,10 +132,17 @@ def draw(commands, args, filling=None, colors=None, opacity=1.0, background=1.0,
     background = _unit_numbers(name, "background", [background] * 3 if isinstance(background, (int, float)) else background)
     if len(background) != 3:
         raise ValueError(f"{name}: background is a number or three; got {len(background)} values")
-    paint = torch.empty(N, G, 4, dtype=torch.float32, device=device)
-    paint[..., :3] = 0.0 if colors is None else _per_group(name, "colors", colors, N, G, (3,), device)
-    paint[..., 3] = (_unit_numbers(name, "opacity", [opacity])[0] if isinstance(opacity, (int, float))
-                     else _per_group(name, "opacity", opacity, N, G, (), device))
+    rgb = 0.0 if colors is None else _per_group(name, "colors", colors, N, G, (3,), device, keep_graph)
+    opaque = (_unit_numbers(name, "opacity", [opacity])[0] if isinstance(opacity, (int, float))
+              else _per_group(name, "opacity", opacity, N, G, (), device, keep_graph))
+    if keep_graph and any(torch.is_tensor(t) and t.requires_grad for t in (rgb, opaque)):
+        rgb = rgb if torch.is_tensor(rgb) else torch.full((), rgb, dtype=torch.float32, device=device)
+        opaque = opaque if torch.is_tensor(opaque) else torch.full((), opaque, dtype=torch.float32, device=device)
+        paint = torch.cat([rgb.expand(N, G, 3), opaque.expand(N, G).unsqueeze(-1)], -1)
+    else:
+        paint = torch.empty(N, G, 4, dtype=torch.float32, device=device)
+        paint[..., :3] = rgb
+        paint[..., 3] = opaque
     modes = None
     if not compound:
         if filling is None:
@@ -128,8 +152,7 @@ def draw(commands, args, filling=None, colors=None, opacity=1.0, background=1.0,
                 raise ValueError(f"{name}: filling is an int tensor {[N, G]} or {[N, G, 1]}; got "
                                  f"{tuple(filling.shape) if torch.is_tensor(filling) else type(filling).__name__}")
             modes = filling.detach().reshape(N, G).to(device=device, dtype=torch.int32).contiguous()
-    return ops.draw(commands, args, modes, paint, background=background, size=size, stroke_width=stroke_width,
-                    evenodd=fill_rule == "evenodd", compound=("fill" if fill else "stroke") if compound else None, n=n, groups=G)
+    return commands, args, G, modes, paint, background
 
 
 def palette(G, device=None):
@@ -202,6 +225,81 @@ def refine_to_images(commands, args, target_images, steps=150, lr=0.1, **raster)
         value = image_loss(commands, refined, targets[0], **raster)["loss"]
         for target in targets[1:]:
             value = value + image_loss(commands, refined, target, **raster)["loss"]
+        return value
+
+    return _adam_refine(args, steps, lr, batch_loss)
+
+
+class _Draw(torch.autograd.Function):
+    """ops.draw_fwd_nn (segments -> raster_sweep_layers_nn); backward ops.draw_bwd (raster_blend_bwd -> raster_sweep_layers_bwd ->
+    the transpose of the chord builder)"""
+
+    @staticmethod
+    def forward(ctx, commands, args, paint, modes, background, size, stroke_width, evenodd, compound, n, groups):
+        paint = paint.contiguous()
+        out, saved = ops.draw_fwd_nn(commands, args, modes, paint, background=background, size=size, stroke_width=stroke_width,
+                                     evenodd=evenodd, compound=compound, n=n, groups=groups)
+        segs, seg_counts, layer_first, cov, idx = saved
+        ctx.save_for_backward(commands, paint, modes, segs, seg_counts, layer_first, cov, idx)
+        ctx.draw = (background, stroke_width, compound, n, groups)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        commands, paint, modes, *saved = ctx.saved_tensors
+        background, stroke_width, compound, n, groups = ctx.draw
+        dargs, dpaint = ops.draw_bwd(commands, modes, paint, tuple(saved), dout.contiguous(), background=background,
+                                     stroke_width=stroke_width, compound=compound, n=n, groups=groups)
+        return (None, dargs, dpaint) + (None,) * 8
+
+
+def draw_with_grad(commands, args, filling=None, colors=None, opacity=1.0, background=1.0, size=64, stroke_width=3.2, fill=False,
+                   fill_rule="nonzero", compound=False, n=10):
+    """`draw` for inputs that receive a gradient: the same arguments, the same checks and the same picture bit for bit, and
+    d picture / d args flows back to float32 `args`, d picture / d colors to a `colors` tensor that requires grad ([G, 3] or
+    [N, G, 3]) and d picture / d opacity to an `opacity` tensor that requires grad ([G] or [N, G]); a per-group table receives
+    the sum over the icons.  The formulas are in the module docstring and in include/dsvg.h ("Layered images: the
+    gradient"): a colour or an opacity outside 0..1 is clamped by the kernel and gets an exact 0, as do the colours of ERASE
+    layers and of groups without chords; `filling` and the winding number carry none.  `commands` of any dtype are read as
+    float32; the backward is not differentiable again."""
+    name = "draw_with_grad"
+    if args.dtype != torch.float32:
+        raise ValueError(f"{name}: float32 args (integer arguments have no gradient); got {args.dtype}")
+    commands, flat_args, G, modes, paint, background = _draw_inputs(name, commands, args, filling, colors, opacity, background,
+                                                                    fill, fill_rule, compound, keep_graph=True)
+    return _Draw.apply(commands, flat_args, paint, modes, tuple(background), int(size), float(stroke_width),
+                       fill_rule == "evenodd", ("fill" if fill else "stroke") if compound else None, int(n), G)
+
+
+def picture_loss(commands, args, target_pictures, **draw):
+    """Mean squared difference between the pictures of `commands` / `args` and `target_pictures` f32 [N, 3, size, size] (the size
+    is the target's) -> {"loss": 0-d, the batch mean; "per_icon": [N]}.  Differentiable with respect to float32 `args`, and
+    to `colors` / `opacity` tensors that require grad.  `draw`: every other argument of `draw_with_grad`."""
+    if target_pictures.dim() != 4 or target_pictures.shape[1] != 3 or target_pictures.shape[-1] != target_pictures.shape[-2]:
+        raise ValueError(f"picture_loss: target_pictures (N, 3, size, size); got {tuple(target_pictures.shape)}")
+    pictures = draw_with_grad(commands, args, size=target_pictures.shape[-1], **draw)
+    if pictures.shape != target_pictures.shape:
+        raise ValueError(f"picture_loss: {pictures.shape[0]} pictures against {target_pictures.shape[0]} targets")
+    per_icon = (pictures - target_pictures.detach().to(pictures.dtype)).pow(2).flatten(1).mean(1)
+    return {"loss": per_icon.mean(), "per_icon": per_icon}
+
+
+def refine_to_pictures(commands, args, target_pictures, steps=150, lr=0.1, **draw):
+    """`refine_to_images` against layered pictures: the Adam loop minimises `picture_loss` on a float32 copy of `args` ->
+    (refined args f32, history f32 [steps]: the loss before each step, kept on the device).  `target_pictures`: one tensor
+    [N, 3, size, size], or a list of such tensors of different sizes (coarse to fine) whose losses are summed.  With a
+    `filling` that erases, the outline of a hole is pulled on like any other: what `image_loss(fill=True)`, which paints holes
+    over, cannot see.  The gradient is as local as that of `refine_to_images`.  Elements whose gradient is always zero (columns
+    0-4, padding, rows that neither draw nor precede a drawing row) come back as they went in."""
+    targets = [target_pictures] if torch.is_tensor(target_pictures) else list(target_pictures)
+    if not targets:
+        raise ValueError("refine_to_pictures: no target pictures")
+
+    def batch_loss(refined):
+        value = picture_loss(commands, refined, targets[0], **draw)["loss"]
+        for target in targets[1:]:
+            value = value + picture_loss(commands, refined, target, **draw)["loss"]
         return value
 
     return _adam_refine(args, steps, lr, batch_loss)

@@ -62,7 +62,9 @@ extern "C" {
  *     assembly over a float32 store with the augmentation applied on load), on the same terms.
  *     Still 19: dsvg_raster_segments_layers / dsvg_raster_sweep_layers added (layered RGB images: per-group outline, fill and
  *     erase, colours and opacities), on the same terms.
- *     Still 19: dsvg_overlap_counts / dsvg_filling_from_counts added (filling of a decoded batch), on the same terms. */
+ *     Still 19: dsvg_overlap_counts / dsvg_filling_from_counts added (filling of a decoded batch), on the same terms.
+ *     Still 19: dsvg_raster_sweep_layers_nn / dsvg_raster_blend_bwd / dsvg_raster_sweep_layers_bwd /
+ *     dsvg_raster_segments_layers_bwd added (the gradient of a layered image), on the same terms. */
 #define DSVG_ABI_VERSION 19
 
 const char* dsvg_last_error(void);
@@ -674,7 +676,7 @@ int dsvg_raster_segments_bwd(const float* commands, const float* dsegs, const in
  * an erase path (the per-group `filling` of the reference's data path, deepsvg/svglib/svg_path.py:29-32), with a colour and
  * an opacity per group - what SVG.draw / draw_colored show (svglib/svg.py:172-221).  Geometry, pixels, the distance to a
  * chord and the half-open crossing rule are those of the section above; tests/raster_layers_ref.py restates the rest in
- * float64.  No gradient.  The definition:
+ * float64.  These two entry points carry no gradient ("Layered images: the gradient" below does).  The definition:
  *  layers: group g of an image is layer g; layers are painted in group order onto a canvas of three channels that starts at
  *    `background`; 1 = paper white, 0 = black.  A layer without chords is skipped.  All arithmetic is fp32.
  *  mode of a layer (modes int32 [B, G]): DSVG_LAYER_FILL, DSVG_LAYER_ERASE, every other value DSVG_LAYER_OUTLINE.
@@ -714,6 +716,43 @@ int dsvg_raster_segments_layers(int32_t itype, const void* commands, const void*
 int dsvg_raster_sweep_layers(const void* segs, const int32_t* seg_counts, const int32_t* layer_first, const int32_t* modes,
                              const float* paint, const float* background, int64_t B, int64_t cap, int32_t G, int32_t size,
                              float stroke_width, int32_t flags, float* out, void* stream);
+/* Layered images: the gradient (still ABI 19: additions only; tests/raster_layers_grad_ref.py restates it in float64).
+ * Per pixel, with the layers that have chords g = 1..K in group order: C_0 = background, alpha_g = opacity_g * cov_g, C_g =
+ * fmaf(alpha_g, p_g - C_{g-1}, C_{g-1}) per channel, out = C_K; p_g is the layer's colour, or the background for an ERASE
+ * layer.  With T_g = prod_{k > g} (1 - alpha_k) (a running product from the top layer down: nothing is ever divided by
+ * 1 - alpha, which is 0 inside every opaque fill):
+ *    d out_c / d alpha_g = T_g (p_g,c - C_{g-1,c}),   d out_c / d p_g,c = T_g alpha_g (an exact 0 for ERASE and skipped layers),
+ *    d alpha_g / d cov_g = opacity_g,   d alpha_g / d opacity_g = cov_g.
+ *  Colours and opacities are clamped by the kernel: the gradient passes where the given value lies in 0..1 and is an exact 0
+ *  where it was clamped or is a NaN.  d cov / d d = -1 / s for OUTLINE, and for FILL and ERASE where cov <= 0.5, +1 / s for FILL
+ *  and ERASE where cov > 0.5, 0 where the stored cov is 0 or 1.  d d / d a and d d / d b are those of dsvg_raster_sweep_bwd with
+ *  the nearest chord taken among the layer's OWN chords (ties to the lowest record index, d == 0 contributes nothing).  The
+ *  winding number carries no gradient under either fill rule.
+ *  raster_sweep_layers_nn: dsvg_raster_sweep_layers (same arguments, `out` with the same bits, with and without
+ *    DSVG_RASTER_CULL) that also writes cov fp32 [B, NL, size, size], the clamped coverage of every layer (0 for a layer without
+ *    chords), and idx int32 [B, NL, size, size]: the image-wide record index of the layer's nearest chord where 0 < cov < 1, -1
+ *    elsewhere; both are the same with and without DSVG_RASTER_CULL.  NL = G, or 1 with DSVG_RASTER_COMPOUND.
+ *  raster_blend_bwd: cov as above, the tables, paint and background of the forward (same DSVG_RASTER_COMPOUND / _FILL) and dout
+ *    fp32 [B, 3, size, size] -> dcov fp32 [B, NL, size, size] = dL / d cov, every element written (0 for a layer without
+ *    chords), and dpaint fp32 [B, G, 4] (16-byte aligned) = dL / d (r, g, b, opacity) summed over the pixels of the image, every
+ *    element written.  One workgroup per image; the pixel sums run in a fixed order without atomics: bit-reproducible.
+ *  raster_sweep_layers_bwd: the records and tables, cov and idx of raster_sweep_layers_nn and dcov -> dsegs fp32 [B, cap, 4] as
+ *    dsvg_raster_sweep_bwd writes it (rows below seg_counts[b] all written; DSVG_RASTER_WIDE as there).  The layer of a record
+ *    is found from layer_first with the forward's clamping; its mode decides the sign rule and the reach.
+ *  raster_segments_layers_bwd: dsvg_raster_segments_bwd with `fill` per group from modes: the transpose of
+ *    dsvg_raster_segments_layers for fp32 inputs -> dargs fp32 [B*G, L, 11], every element written.  A compound image has the
+ *    records of dsvg_raster_segments: its dsegs go to dsvg_raster_segments_bwd. */
+int dsvg_raster_sweep_layers_nn(const void* segs, const int32_t* seg_counts, const int32_t* layer_first, const int32_t* modes,
+                                const float* paint, const float* background, int64_t B, int64_t cap, int32_t G, int32_t size,
+                                float stroke_width, int32_t flags, float* out, float* cov, int32_t* idx, void* stream);
+int dsvg_raster_blend_bwd(const float* cov, const int32_t* seg_counts, const int32_t* layer_first, const int32_t* modes,
+                          const float* paint, const float* background, const float* dout, int64_t B, int64_t cap, int32_t G,
+                          int32_t size, int32_t flags, float* dcov, float* dpaint, void* stream);
+int dsvg_raster_sweep_layers_bwd(const void* segs, const int32_t* seg_counts, const int32_t* layer_first, const int32_t* modes,
+                                 const float* cov, const int32_t* idx, const float* dcov, int64_t B, int64_t cap, int32_t G,
+                                 int32_t size, float stroke_width, int32_t flags, float* dsegs, void* stream);
+int dsvg_raster_segments_layers_bwd(const float* commands, const float* dsegs, const int32_t* seg_counts, const int32_t* modes,
+                                    int64_t B, int32_t G, int32_t L, int32_t n, float* dargs, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Canonical path order of a batch (csrc/paths.hip): SVG.canonicalize() (deepsvg/svglib/svg.py:333-349) applied to
