@@ -9,6 +9,8 @@ Public surface mirrors the reference (alexandre01/deepsvg):
     deepsvg_amd.render          <->  deepsvg.svglib: SVG.draw of a decoded batch (stroke / fill coverage images, interpolation)
     deepsvg_amd.paths           <->  deepsvg.svglib: SVG.canonicalize + numericalize of a batch (the form the encoder was trained on),
                                      its preprocessing chain, and SVG.zoom / rotate / translate / normalize
+    deepsvg_amd.svgio           <->  deepsvg.svglib: SVG.load_svg of a batch of documents (path text parsed on the device), the
+                                     dataset/preprocess.py chain over files, and the way back out as SVG text
     deepsvg_amd.dataset         <->  deepsvg.svgtensor_dataset (stored augmentations); deepsvg_amd.svg_dataset <-> deepsvg.svg_dataset
                                      (augmentation on the fly); both imported by name, as cfg.dataloader_module
 """
@@ -22,6 +24,7 @@ from .loss import SVGLoss  # noqa: F401
 from . import metrics  # noqa: F401
 from . import render  # noqa: F401
 from . import paths  # noqa: F401
+from . import svgio  # noqa: F401
 
 __all__ = ["SVGTransformer", "SVGLoss", "_DefaultConfig", "Hierarchical", "HierarchicalOrdered", "OneStageOneShot", "metrics",
-           "render", "paths"]
+           "render", "paths", "svgio"]

@@ -12,7 +12,7 @@ mkdir -p "$OUT" obj
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-gpu-rdc -Wno-unused-result -Wno-unused-value"
 HDRS="$(LC_ALL=C ls *.h) ../../include/dsvg.h"     # taken from the directory: a new header cannot be left out of the key
 HSHA=$( (echo "$FLAGS"; cat $HDRS) | sha256sum | cut -d' ' -f1)
-SRCS="gemm gemm_bf16 gemm_bf16_glds layernorm attention attention_mfma attention_long_mfma embed loss optim assemble match long_seq ffn_fused attn_fused group_stage head_fused pack_images ffn_bwd_gate metrics raster paths paths_expand paths_simplify paths_transform paths_fill"
+SRCS="gemm gemm_bf16 gemm_bf16_glds layernorm attention attention_mfma attention_long_mfma embed loss optim assemble match long_seq ffn_fused attn_fused group_stage head_fused pack_images ffn_bwd_gate metrics raster paths paths_expand paths_simplify paths_transform paths_fill svg_parse"
 pids=()
 names=()
 for f in $SRCS; do

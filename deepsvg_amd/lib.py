@@ -22,6 +22,10 @@ DSVG_RASTER_WIDE = 4                           # flag of dsvg_raster_sweep_bwd: 
 DSVG_RASTER_EVENODD, DSVG_RASTER_COMPOUND = 8, 16      # flags of dsvg_raster_sweep_layers
 DSVG_LAYER_OUTLINE, DSVG_LAYER_FILL, DSVG_LAYER_ERASE = 0, 1, 2       # the mode table of the layered rasteriser
 DSVG_FILLING_EVENODD, DSVG_FILLING_ORIENTATION = 0, 1                 # rules of dsvg_filling_from_counts
+DSVG_SVG_PATH, DSVG_SVG_POLYLINE, DSVG_SVG_POLYGON = 0, 1, 2         # kinds of dsvg_svg_parse
+(DSVG_SVG_OK, DSVG_SVG_EMPTY, DSVG_SVG_ARG_COUNT, DSVG_SVG_SLOW_NUMBER, DSVG_SVG_ROWS_OVERFLOW, DSVG_SVG_BAD_SLOT,
+ DSVG_SVG_RANGE) = range(7)                                           # its status codes
+DSVG_SVG_TILE = 64                                                    # bytes of a string one wave reads at a time
 # == DSVG_ABI_VERSION of include/dsvg.h at the time SIGNATURES below was written: load() refuses a library built from another
 # header (a stale .so with the old argument lists would otherwise be called with a stream where a size is expected)
 ABI_VERSION = 19
@@ -140,6 +144,7 @@ SIGNATURES = {
     "dsvg_assemble_augmented": (c_i32, [vp, c_i64, vp, c_i64, vp, c_i64, c_i32, c_i32, c_i32, c_f32, c_i32, c_i32, c_u32, vp,
                                         c_i32, vp, vp, vp, vp]),
     "dsvg_paths_transform": (c_i32, [vp, vp, c_i64, c_i32, c_i32, c_i32, c_u32, vp, c_i32, vp, vp]),
+    "dsvg_svg_parse": (c_i32, [vp, c_i64, vp, vp, vp, c_i64, c_i64, c_i32, c_i32, vp, vp, vp, vp, vp, vp, vp]),
     "dsvg_attention_causal_fwd": (c_i32, [c_i32, vp, vp, vp, c_i64, c_i32, c_i32, c_f32, c_f32, c_u32, vp, vp]),
     "dsvg_attention_causal_bwd": (c_i32, [c_i32, vp, vp, vp, vp, c_i64, c_i32, c_i32, c_f32, c_f32, c_u32, vp, vp]),
     "dsvg_seq_lens": (c_i32, [vp, c_i64, c_i32, c_i32, vp, vp]),

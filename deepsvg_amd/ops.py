@@ -1831,6 +1831,36 @@ def paths_transform(commands, args, kinds, params, numericalize=0):
     return out
 
 
+def svg_parse(data, offsets, kind, slot, N, G, S):
+    """data uint8 [B], offsets int64 [P + 1], kind uint8 [P], slot int32 [P] on the device; S >= 2, G * S <= 2048 -> the dict
+    of deepsvg_amd.svgio.parse_paths: "commands" [N, G, S] / "args" [N, G, S, 11] float32, "len_groups" int32 [N, G],
+    "status" int32 [P], "valid" bool [N].  Five launches (csrc/svg_parse.hip) and a workspace of 2 N G int32; nothing is read
+    back; include/dsvg.h has the definition"""
+    _chk(data, offsets, kind, slot)
+    assert data.dtype == torch.uint8 and data.dim() == 1 and data.is_contiguous()
+    assert offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.numel() >= 2 and offsets.is_contiguous()
+    P = offsets.numel() - 1
+    assert kind.dtype == torch.uint8 and kind.shape == (P,) and kind.is_contiguous()
+    assert slot.dtype == torch.int32 and slot.shape == (P,) and slot.is_contiguous()
+    N, G, S = int(N), int(G), int(S)
+    dev = offsets.device
+    out_c = torch.empty(N, G, S, dtype=torch.float32, device=dev)
+    out_a = torch.empty(N, G, S, N_ARGS, dtype=torch.float32, device=dev)
+    len_groups = torch.empty(N, G, dtype=torch.int32, device=dev)
+    status = torch.empty(P, dtype=torch.int32, device=dev)
+    valid = torch.empty(N, dtype=torch.bool, device=dev)
+    ws = torch.empty(2 * N * G, dtype=torch.int32, device=dev)
+    if data.numel() == 0:
+        data = torch.zeros(1, dtype=torch.uint8, device=dev)        # a pointer to hand over; B = 0 keeps it unread
+        B = 0
+    else:
+        B = data.numel()
+    _l.check(_l.load().dsvg_svg_parse(data.data_ptr(), B, offsets.data_ptr(), kind.data_ptr(), slot.data_ptr(), P, N, G, S,
+                                      ws.data_ptr(), out_c.data_ptr(), out_a.data_ptr(), len_groups.data_ptr(),
+                                      status.data_ptr(), valid.data_ptr(), _stream()), "dsvg_svg_parse")
+    return {"commands": out_c, "args": out_a, "len_groups": len_groups, "status": status, "valid": valid}
+
+
 def assemble_augmented(rows, slot_off, variant, G, L, grouped, kinds, params, numericalize=256, want_args=True,
                        want_rel=False, pad_val=-1.0, args_dim=256):
     """`assemble_batch` over a float32 store: rows float32 [R, 12], slot_off int32 [n_variants*G + 1], variant int32 [N];

@@ -49,9 +49,11 @@ csrc/paths_transform.hip (include/dsvg.h has its definition, tests/paths_transfo
 tests/golden/paths/transform.npz compares with the reference by equality): `normalize` and `zoom` before it
 (``svg.normalize().zoom(0.9)``, svg_dataset.py:112-116), `augment` with ``numericalize`` behind it (``SVGDataset._augment``
 and ``SVG.numericalize(256)``, svg_dataset.py:137-156).  The whole chain of the reference's on-the-fly data set is then
-``arcs_to_beziers -> normalize(viewbox, 24) -> zoom(0.9, viewbox=24) -> canonicalize -> simplify_heuristic(unit=1) ->
-dataset.PackedSVGStore.from_batch(viewbox=24) -> svg_dataset.SVGDataset.batch``, the last link drawing fresh
-augmentation parameters on the device for every batch and applying them while it assembles the model's tensors.
+``svgio.load_svgs -> arcs_to_beziers -> normalize(viewbox, 24) -> zoom(0.9, viewbox=24) -> canonicalize ->
+simplify_heuristic(unit=1) -> dataset.PackedSVGStore.from_batch(viewbox=24) -> svg_dataset.SVGDataset.batch``, the first
+link reading the text of SVG files on the device (`deepsvg_amd.svgio`, which also composes the links up to the store as
+`svgio.preprocess` / `svgio.preprocess_files`), the last link drawing fresh augmentation parameters on the device for every
+batch and applying them while it assembles the model's tensors.
 
 `compute_filling` gives a decoded batch the per-group ``filling`` (0 = OUTLINE, 1 = FILL, 2 = ERASE) that `render.draw`,
 ``PackedSVGStore.from_batch`` and ``SVGDataset`` take and that tensors do not carry: ``SVGPathGroup.compute_filling`` over

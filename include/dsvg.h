@@ -64,7 +64,9 @@ extern "C" {
  *     erase, colours and opacities), on the same terms.
  *     Still 19: dsvg_overlap_counts / dsvg_filling_from_counts added (filling of a decoded batch), on the same terms.
  *     Still 19: dsvg_raster_sweep_layers_nn / dsvg_raster_blend_bwd / dsvg_raster_sweep_layers_bwd /
- *     dsvg_raster_segments_layers_bwd added (the gradient of a layered image), on the same terms. */
+ *     dsvg_raster_segments_layers_bwd added (the gradient of a layered image), on the same terms.
+ *     Still 19: dsvg_svg_parse added (SVG path text to padded rows for a whole batch), on the same terms: four host tests pin 19
+ *     for the bindings they cover, and no exported signature changed. */
 #define DSVG_ABI_VERSION 19
 
 const char* dsvg_last_error(void);
@@ -1072,6 +1074,76 @@ int dsvg_assemble_augmented(const float* rows, int64_t n_rows, const int32_t* sl
                             const int32_t* variant, int64_t n_items, int32_t G, int32_t grouped, int32_t L,
                             float pad_val, int32_t args_dim, int32_t K, uint32_t kinds, const float* params,
                             int32_t numericalize, float* commands, float* args, float* args_rel, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * SVG path text -> padded rows (csrc/svg_parse.hip): the reference's SVGPath.from_str(s).to_tensor() (svglib/svg_path.py:79-157,
+ * svg_command.py:51-120) and the `points` lists of SVGPolyline / SVGPolygon (svg_primitive.py:196-207) for P strings at once.
+ * tests/svgio_ref.py restates everything below in plain Python; tests/golden/svgio/parse.npz holds the reference's results.
+ *  input: data uint8 [B], the UTF-8 bytes of the strings back to back; offsets int64 [P + 1] (clamped to [0, B] and to each
+ *    other on the device: no offset can make a read leave the buffer); kind uint8 [P]: DSVG_SVG_PATH a `d` attribute,
+ *    DSVG_SVG_POLYLINE / DSVG_SVG_POLYGON a `points` list (any other value reads as PATH); slot int32 [P]: the output group
+ *    n * G + g the string fills, -1 = status only.
+ *  tokens: a command letter is one of MmZzLlHhVvCcSsQqTtAa (kind PATH only; in a points list every letter is a separator).
+ *    Numbers are what re.findall finds for [-+]?[0-9]*\.?[0-9]+(?:[eE][-+]?[0-9]+)? - leftmost, greedy, with backtracking -
+ *    stated as an automaton over the byte classes digit, dot, sign, e/E, other (bytes >= 0x80 included) with the states
+ *    IDLE, SIGN, DOT0 ([sign] dot, no digit yet), INT, INTDOT, FRAC, EXP0 (number, e), EXPSIGN (number, e, sign), EXPD:
+ *                 digit   dot      sign      e      other
+ *      IDLE       INT     DOT0     SIGN      IDLE   IDLE
+ *      SIGN       INT     DOT0     SIGN      IDLE   IDLE
+ *      DOT0       FRAC    DOT0     SIGN      IDLE   IDLE
+ *      INT        INT     INTDOT   SIGN      EXP0   IDLE
+ *      INTDOT     FRAC    DOT0     SIGN      IDLE   IDLE
+ *      FRAC       FRAC    DOT0     SIGN      EXP0   IDLE
+ *      EXP0       EXPD    DOT0     EXPSIGN   IDLE   IDLE
+ *      EXPSIGN    EXPD    DOT0     SIGN      IDLE   IDLE
+ *      EXPD       EXPD    DOT0     SIGN      IDLE   IDLE
+ *    INT, FRAC and EXPD accept.  A number goes on from INT with digit / dot / e, from FRAC with digit / e, from EXP0 with
+ *    digit / sign, from INTDOT, EXPSIGN and EXPD with a digit; on any other byte it ends at its last accepting byte (1 byte
+ *    back from INTDOT and EXP0, 2 from EXPSIGN: `1.` is 1, `4e` is 4, `4e+` is 4) and the bytes behind that are read again as
+ *    from IDLE, which the table's rows already say.  A number starts at a byte that leads to SIGN, to INT from IDLE, or to
+ *    DOT0 from anything but SIGN; from EXPSIGN to DOT0 it starts one byte earlier (`4e+.5` is 4 and +.5).  So `1.5.5` is 1.5
+ *    and .5, `10-2e1` is 10 and -20, and a sign not followed by a digit or .digit is skipped.  One separator is read behind
+ *    the last byte.  Numbers in front of the first command letter are dropped unread.
+ *  value: sign, then leading zeros and the trailing zeros of the fraction dropped, the remaining digits an integer w, e10 =
+ *    exponent - fraction digits kept.  With w < 2^53 and |e10| <= 22 the value is (double)w * 10^e10 (e10 >= 0) or (double)w /
+ *    10^-e10: one correctly rounded operation on exact operands, equal to strtod / Python's float() bit for bit; -0 keeps its
+ *    sign.  Anything else (more digits, an accumulator past 2^64, a larger exponent) is DSVG_SVG_SLOW_NUMBER.
+ *  commands: per letter with k numbers behind it.  z: k = 0, and the position returns to the sub-path's initial position.
+ *    Any other letter: k > 0 and a multiple of its arity (m l t 2; h v 1; c 6; s q 4; a 7), k / arity commands; k = 0 is
+ *    DSVG_SVG_ARG_COUNT like every other miscount (the reference indexes its empty command list and raises).  An m with more
+ *    than 2 numbers is a move and then l on the rest.  ARITHMETIC IS FLOAT32: every number is rounded to fp32 when it becomes
+ *    a coordinate (the reference's Point is a float32 array, svglib/geom.py:60-75), a lower-case letter then adds the current
+ *    position in fp32, one rounding per add (Point.translate); radii, angle and flags are never translated, and a flag is
+ *    trunc(value).  h and v take the other coordinate from the current position.  q is a c with both control points the
+ *    quadratic's one (the reference's rule, not degree elevation).  s and t: control1 = fl(2 pos - control2 of the command
+ *    before) when that was a Bezier of any letter, else pos; control2 is given (s) or equals control1 (t).
+ *  rows (SVGPath.from_commands, allow_empty=False, add_closing=False): commands in front of the first move, and behind a z
+ *    until the next move, move the position and write nothing; a move opens a sub-path, and a sub-path without a command
+ *    writes nothing, neither m nor z; otherwise m (the move's target), its rows, and z when it was closed.  Arcs stay `a`
+ *    rows.  POLYLINE / POLYGON: an even count of numbers, rows m p0, l p1, ... and z for a polygon (no closing line); fewer
+ *    than 2 points leave no row.
+ *  output, framed as dsvg_paths_expand frames its result: commands [N, G, S] / args [N, G, S, 11] fp32 (SOS, the rows, EOS...;
+ *    -1 in every slot CMD_ARGS_MASK does not enable, a z row all -1; a group nobody fills is SOS, EOS...), len_groups int32
+ *    [N, G], status int32 [P], valid uint8 [N].  status, in this order of precedence: BAD_SLOT (slot outside [-1, N G) or
+ *    shared by two strings; such a string is not parsed); the first ARG_COUNT or SLOW_NUMBER in reading order; ROWS_OVERFLOW
+ *    (more than S - 2 rows); RANGE (a written value is not finite in fp32); EMPTY (no row: not an error); OK.  An icon is
+ *    valid when every string with a slot inside it is OK or EMPTY; an invalid icon is SOS, EOS... in every group with
+ *    len_groups 0.  workspace: int32 [2 N G].  Five launches on one stream, no atomics, nothing read back, every output element
+ *    written: bit-reproducible, capturable. */
+#define DSVG_SVG_PATH 0
+#define DSVG_SVG_POLYLINE 1
+#define DSVG_SVG_POLYGON 2
+#define DSVG_SVG_OK 0
+#define DSVG_SVG_EMPTY 1
+#define DSVG_SVG_ARG_COUNT 2
+#define DSVG_SVG_SLOW_NUMBER 3
+#define DSVG_SVG_ROWS_OVERFLOW 4
+#define DSVG_SVG_BAD_SLOT 5
+#define DSVG_SVG_RANGE 6
+#define DSVG_SVG_TILE 64 /* bytes of a string one wave reads at a time */
+int dsvg_svg_parse(const uint8_t* data, int64_t B, const int64_t* offsets, const uint8_t* kind, const int32_t* slot,
+                   int64_t P, int64_t N, int32_t G, int32_t S, int32_t* workspace, float* commands, float* args,
+                   int32_t* len_groups, int32_t* status, uint8_t* valid, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Fused FFN sub-block, bf16, d_model = 256 / dim_feedforward = 512 (csrc/ffn_fused.hip):
