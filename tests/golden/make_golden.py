@@ -83,6 +83,17 @@ def build_cfg(kind):
         cfg = ref_cfg.Hierarchical()
         cfg.label_condition = True
         cfg.dim_z = 128
+    elif kind in ("narrow128", "narrow128_1s"):     # off the default width (tests/helpers.py _width_cfg): d128 / 4 heads / ff256
+        cfg = ref_cfg.Hierarchical() if kind == "narrow128" else ref_cfg.OneStageOneShot()
+        cfg.d_model, cfg.n_heads, cfg.dim_feedforward, cfg.dim_z = 128, 4, 256, 128
+        cfg.n_layers = cfg.n_layers_decode = 2
+        if kind == "narrow128":
+            cfg.max_num_groups = cfg.num_groups_proposal = 4
+            cfg.max_seq_len = 12
+            cfg.max_total_len = 48
+        else:
+            cfg.max_total_len = 50
+        cfg.use_vae = False
     else:
         raise ValueError(kind)
     return cfg
@@ -94,7 +105,7 @@ def run_case(name, kind, n, seed, wseed):
     model = RefModel(cfg)
     sd = det_state_dict(model, seed=wseed)
     model.load_state_dict(sd)
-    if kind in ("onestage", "sketchformer", "onestage_label", "onestage240", "sketchformer240"):
+    if kind in ("onestage", "sketchformer", "onestage_label", "onestage240", "sketchformer240", "narrow128_1s"):
         commands, args = make_batch_onestage(n, total_len=cfg.max_total_len, seed=seed)
     else:
         commands, args = make_batch(n, G=cfg.max_num_groups, S=cfg.max_seq_len, seed=seed)
@@ -251,7 +262,8 @@ if __name__ == "__main__":
                "fonts_label_n4": ("fonts", 4, 15, 1234), "selfmatch_n6": ("selfmatch", 6, 16, 1234),
                "sketchformer50_n4": ("sketchformer", 4, 17, 1234), "onestage50_label_n3": ("onestage_label", 3, 18, 1234),
                "hier_rel_n3": ("hier_rel", 3, 19, 1234), "onestage240_n2": ("onestage240", 2, 20, 1234),
-               "sketchformer240_n2": ("sketchformer240", 2, 21, 1234)}
+               "sketchformer240_n2": ("sketchformer240", 2, 21, 1234), "narrow128_n3": ("narrow128", 3, 22, 1234),
+               "narrow128_1s_n3": ("narrow128_1s", 3, 23, 1234)}
         for nm in sys.argv[1:]:
             run_case(nm, *ALL[nm])
         sys.exit(0)
@@ -266,3 +278,5 @@ if __name__ == "__main__":
     run_case("hier_rel_n3", "hier_rel", 3, 19, 1234)
     run_case("onestage240_n2", "onestage240", 2, 20, 1234)
     run_case("sketchformer240_n2", "sketchformer240", 2, 21, 1234)
+    run_case("narrow128_n3", "narrow128", 3, 22, 1234)
+    run_case("narrow128_1s_n3", "narrow128_1s", 3, 23, 1234)

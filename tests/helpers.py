@@ -80,9 +80,74 @@ def build_cfg(kind):
         cfg = C.Hierarchical()
         cfg.label_condition = True
         cfg.dim_z = 128
+    elif kind in WIDTH_KINDS:
+        cfg = _width_cfg(kind)
     else:
         raise ValueError(kind)
     return cfg
+
+
+# configurations off the default width (d_model 256 / 8 heads / dim_feedforward 512 / 8 groups of 30 commands): none of
+# them fits a fused kernel, every layer takes the general kernels.  tests/golden/make_golden.py builds the same ones
+# from the reference's classes for the two kinds that have a fixture (narrow128, narrow128_1s).
+WIDTH_KINDS = ("narrow128", "narrow128_vae", "narrow128_1s", "narrow128_ar", "narrow128_match", "odd192", "odd192_1s",
+               "odd96", "wide512", "ff1024", "nores")
+ONE_STAGE_KINDS = ("onestage", "sketchformer", "onestage_label", "onestage240", "sketchformer240", "narrow128_1s",
+                   "narrow128_ar", "odd192_1s")
+
+
+def _set_width(cfg, d_model, n_heads, dim_ff, dim_z, layers, G=None, S=None, total=None):
+    cfg.d_model, cfg.n_heads, cfg.dim_feedforward, cfg.dim_z = d_model, n_heads, dim_ff, dim_z
+    cfg.n_layers = cfg.n_layers_decode = layers
+    if G is not None:
+        cfg.max_num_groups = cfg.num_groups_proposal = G
+        cfg.max_seq_len = S
+    cfg.max_total_len = total if total is not None else cfg.max_num_groups * cfg.max_seq_len
+    cfg.use_vae = False
+    return cfg
+
+
+def _width_cfg(kind):
+    if kind in ("narrow128", "narrow128_vae"):
+        cfg = _set_width(C.Hierarchical(), 128, 4, 256, 128, 2, G=4, S=12)
+        cfg.use_vae = kind == "narrow128_vae"
+    elif kind == "narrow128_1s":        # 52 tokens on 4 heads
+        cfg = _set_width(C.OneStageOneShot(), 128, 4, 256, 128, 2, total=50)
+    elif kind == "narrow128_ar":        # causal, relative targets
+        cfg = _set_width(C.Sketchformer(), 128, 4, 256, 128, 2, total=50)
+    elif kind == "narrow128_match":     # (the oracle's loss needs num_groups_proposal == max_num_groups)
+        cfg = _set_width(C.HierarchicalSelfMatching(), 128, 4, 256, 128, 2, G=4, S=12)
+    elif kind == "odd192":              # 6 heads: no power of two, 32 % 6 != 0
+        cfg = _set_width(C.Hierarchical(), 192, 6, 384, 256, 1, G=6, S=20)
+    elif kind == "odd192_1s":           # 6 heads x 52 tokens: one head per workgroup
+        cfg = _set_width(C.OneStageOneShot(), 192, 6, 384, 256, 1, total=50)
+    elif kind == "odd96":               # 3 heads: one head per workgroup at every length
+        cfg = _set_width(C.Hierarchical(), 96, 3, 192, 96, 1, G=4, S=12)
+    elif kind == "wide512":
+        cfg = _set_width(C.Hierarchical(), 512, 16, 1024, 64, 1)
+    elif kind == "ff1024":              # fused attention fits, the fused FFN does not
+        cfg = _set_width(C.Hierarchical(), 256, 8, 1024, 256, 1)
+    elif kind == "nores":
+        cfg = _set_width(C.Hierarchical(), 256, 8, 512, 256, 1)
+        cfg.use_resnet = False
+    else:
+        raise ValueError(kind)
+    return cfg
+
+
+def width_batch(cfg, kind, n, seed):
+    """-> (commands, args, args_dec) of n synthetic icons in the layout the kind's model takes"""
+    from deepsvg_amd.synthetic import make_batch, make_batch_onestage
+    if kind in ONE_STAGE_KINDS:
+        commands, args = make_batch_onestage(n, total_len=cfg.max_total_len, seed=seed)
+    else:
+        commands, args = make_batch(n, G=cfg.max_num_groups, S=cfg.max_seq_len, seed=seed)
+    args_dec = args
+    if cfg.rel_targets:
+        from oracle import batch_assembly_oracle as B
+        args_dec = torch.stack([torch.stack([torch.from_numpy(B.relative_args(commands[i, g].numpy(), args[i, g].numpy()))
+                                             for g in range(commands.shape[1])]) for i in range(n)])
+    return commands, args, args_dec
 
 
 def golden_args_dec(g, args):

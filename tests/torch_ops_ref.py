@@ -109,6 +109,11 @@ def _f(t):
     return t.to(torch.float32)
 
 
+def _fa(t):
+    """attention restatement: float64 inputs stay float64 (a high-precision reference), anything else runs in fp32"""
+    return t if t.dtype == torch.float64 else t.to(torch.float32)
+
+
 # ----------------------------------------------------------------------------------------------------
 def gemm(a, b, *, a_kc=True, b_kc=True, bias=None, res=None, res_pre=False, act=0, gate=None, gate_scale=1.0,
          drop_p=0.0, drop_site=0, a_drop_p=0.0, a_drop_site=0, seed=None, out=None, out_dtype=None,
@@ -211,7 +216,7 @@ def _mask_bits(mask, S):
 
 def _attn_probs(qkv, key_mask, n_seq, S, H, scale, causal=False):
     d = 32 * H
-    q, k, v = _f(qkv).view(n_seq, S, 3, H, 32).permute(2, 0, 3, 1, 4)      # each (n_seq, H, S, 32)
+    q, k, v = _fa(qkv).view(n_seq, S, 3, H, 32).permute(2, 0, 3, 1, 4)     # each (n_seq, H, S, 32)
     s = (q * scale) @ k.transpose(-1, -2)
     if causal:          # square_subsequent_mask: query i sees keys j <= i
         s = s.masked_fill(torch.triu(torch.ones(S, S, dtype=torch.bool, device=s.device), diagonal=1), float("-inf"))
@@ -327,7 +332,7 @@ def attention_bwd(qkv, key_mask, dout, n_seq, S, n_heads, scale, drop_p=0.0, dro
     H = n_heads
     q, k, v, P = _attn_probs(qkv, key_mask, n_seq, S, H, scale, causal)
     mult = _attn_drop(drop_p, seed, drop_site, n_seq, S, H, qkv.device)
-    do = _f(dout).view(n_seq, S, H, 32).permute(0, 2, 1, 3)
+    do = _fa(dout).to(q.dtype).view(n_seq, S, H, 32).permute(0, 2, 1, 3)
     dv = (P * mult).transpose(-1, -2) @ do
     dP = (do @ v.transpose(-1, -2)) * mult
     D = (P * dP).sum(-1, keepdim=True)
