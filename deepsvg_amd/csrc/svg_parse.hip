@@ -17,11 +17,14 @@
 //                      walks them: positions are float32 values added one at a time (the reference's `Point` is a float32
 //                      array), which is sequential by definition.  The rows it produces collect in LDS and all lanes write
 //                      them out, 44 contiguous bytes per row.
+//                      dsvg_svg_parse_exact launches the kernel's other instantiation: a number the fast rule above refuses goes
+//                      through the exact rule (decimal_exact.h: integers only) before it is called slow.
 //     svg_finish_kernel  one workgroup per icon: the icon is valid when every string with a slot in it is OK or EMPTY; every
 //                      group that no OK string of a valid icon wrote is written here as SOS, EOS...
 // Every read of text is bounded by the string's offsets clamped to the buffer, every row write by S - 2 rows per group.
 #include "dsvg_common.h"
 #include "svg_seq.h"             // vocabulary, N_ARGS and the argument columns
+#include "decimal_exact.h"       // the exact rule, integers only
 #include "../../include/dsvg.h"
 
 // positions are sums of float32 values, each add rounded once; nothing here may be contracted into a fused multiply-add
@@ -104,7 +107,9 @@ __device__ __forceinline__ bool goes_on(int q, int k) {
 }
 __device__ __forceinline__ int behind(int q) { return q == Q_EXPSIGN ? 2 : (q == Q_INTDOT || q == Q_EXP0) ? 1 : 0; }
 
-// the bytes [lo, hi) of one match -> its float64 value; false outside the fast path
+// the bytes [lo, hi) of one match -> its float64 value; false outside the fast path.  A template, like Walk below, only so that
+// each instantiation of the kernel has a copy of its own with one caller, which the compiler inlines as it did before there were two
+template <bool EXACT>
 __device__ bool decimal(const uint8_t* __restrict__ t, long long lo, long long hi, double& out) {
     constexpr double kPow10[23] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
                                    1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};     // exact in float64
@@ -170,6 +175,7 @@ struct WaveLds {
 
 // SVGCommand.from_str over the tokens and SVGPath.from_commands(allow_empty=False, add_closing=False) over its commands, row
 // by row: lane 0 only
+template <bool EXACT>
 struct Walk {
     float px = 0.f, py = 0.f, ix = 0.f, iy = 0.f;    // position, initial position of the sub-path
     float bx = 0.f, by = 0.f, mx = 0.f, my = 0.f;    // control2 of the previous Bezier; the target of the open move
@@ -346,6 +352,10 @@ __global__ void slots_mark_kernel(const int32_t* __restrict__ slot, long long P,
 }
 
 // ---- one wave per string -------------------------------------------------------------------------------------------------------
+// EXACT = false is the fast rule alone.  EXACT = true: a number the fast rule refuses goes through the exact rule before it is
+// tagged TAG_SLOW - in a branch of its own behind the fast stores, so that the wave runs the long conversion once, with the
+// lanes that need it active, however they are scattered over the tile.
+template <bool EXACT>
 __global__ __launch_bounds__(SV_TILE) void svg_parse_kernel(const uint8_t* __restrict__ data, long long B,
                                                             const int64_t* __restrict__ offsets, const uint8_t* __restrict__ kinds,
                                                             const int32_t* __restrict__ slot, long long P, long long NG, int S,
@@ -369,7 +379,7 @@ __global__ __launch_bounds__(SV_TILE) void svg_parse_kernel(const uint8_t* __res
     float* g_cmd = s >= 0 ? out_cmd + s * S : nullptr;
     float* g_args = s >= 0 ? out_args + s * S * N_ARGS : nullptr;
 
-    Walk walk;                            // lane 0's copy is the one that counts
+    Walk<EXACT> walk;                     // lane 0's copy is the one that counts
     walk.kind = kind == DSVG_SVG_POLYLINE || kind == DSVG_SVG_POLYGON ? kind : DSVG_SVG_PATH;
     walk.cap = S - 2;
     int state = Q_IDLE;                   // behind the last byte of the tile before
@@ -443,11 +453,22 @@ __global__ __launch_bounds__(SV_TILE) void svg_parse_kernel(const uint8_t* __res
         const unsigned long long nb = __ballot(ends), lb = __ballot(letter);
         const unsigned long long below = (1ull << lane) - 1ull;
         const int at = __popcll(nb & below) + __popcll(lb & below);
+        bool refused = false;               // EXACT only: a number inside the string that the fast rule did not take
         if (ends) {
             double v = 0.0;
-            const bool fast = mine >= 0 && mine < end && end <= len && decimal(text, mine, end, v);
+            const bool fast = mine >= 0 && mine < end && end <= len && decimal<EXACT>(text, mine, end, v);
             w.tok_val[at] = v;
             w.tok_tag[at] = fast ? TAG_NUMBER : TAG_SLOW;
+            if constexpr (EXACT) refused = !fast && mine >= 0 && mine < end && end <= len;
+        }
+        if constexpr (EXACT) {
+            if (refused) {
+                double v = 0.0;
+                if (dsvg_exact::decimal_exact(text, mine, end, v)) {
+                    w.tok_val[at] = v;
+                    w.tok_tag[at] = TAG_NUMBER;
+                }
+            }
         }
         if (letter) w.tok_tag[at + (ends ? 1 : 0)] = (uint8_t)b;
         const int total = __popcll(nb) + __popcll(lb);
@@ -508,9 +529,10 @@ __global__ __launch_bounds__(SP_THREADS) void svg_finish_kernel(const int32_t* _
 }
 }  // namespace
 
-extern "C" int dsvg_svg_parse(const uint8_t* data, int64_t B, const int64_t* offsets, const uint8_t* kind, const int32_t* slot,
-                              int64_t P, int64_t N, int32_t G, int32_t S, int32_t* workspace, float* commands, float* args,
-                              int32_t* len_groups, int32_t* status, uint8_t* valid, void* stream) {
+template <bool EXACT>
+static int svg_parse_launch(const uint8_t* data, int64_t B, const int64_t* offsets, const uint8_t* kind, const int32_t* slot,
+                            int64_t P, int64_t N, int32_t G, int32_t S, int32_t* workspace, float* commands, float* args,
+                            int32_t* len_groups, int32_t* status, uint8_t* valid, void* stream) {
     DSVG_CHECK_ARG(data && offsets && kind && slot && workspace && commands && args && len_groups && status && valid,
                    "svg_parse: null pointer");
     DSVG_CHECK_ARG(B >= 0 && B < (1ll << 31) && P >= 1 && P < (1ll << 31), "svg_parse: B = %lld bytes and P = %lld strings, need "
@@ -525,10 +547,25 @@ extern "C" int dsvg_svg_parse(const uint8_t* data, int64_t B, const int64_t* off
     hipLaunchKernelGGL(slots_init_kernel, dim3((unsigned)dsvg_cdiv(NG, 256)), dim3(256), 0, st, owner, shared, NG);
     hipLaunchKernelGGL(slots_claim_kernel, dim3((unsigned)dsvg_cdiv(P, 256)), dim3(256), 0, st, slot, (long long)P, NG, owner);
     hipLaunchKernelGGL(slots_mark_kernel, dim3((unsigned)dsvg_cdiv(P, 256)), dim3(256), 0, st, slot, (long long)P, NG, owner, shared);
-    hipLaunchKernelGGL(svg_parse_kernel, dim3((unsigned)P), dim3(SV_TILE), 0, st, data, (long long)B, offsets, kind, slot,
+    hipLaunchKernelGGL(svg_parse_kernel<EXACT>, dim3((unsigned)P), dim3(SV_TILE), 0, st, data, (long long)B, offsets, kind, slot,
                        (long long)P, NG, S, shared, commands, args, len_groups, status);
     hipLaunchKernelGGL(svg_finish_kernel, dim3((unsigned)N), dim3(SP_THREADS), 0, st, owner, shared, status, (long long)P, G, S,
                        commands, args, len_groups, valid);
     DSVG_LAUNCH_CHECK("svg_parse");
     return 0;
+}
+
+extern "C" int dsvg_svg_parse(const uint8_t* data, int64_t B, const int64_t* offsets, const uint8_t* kind, const int32_t* slot,
+                              int64_t P, int64_t N, int32_t G, int32_t S, int32_t* workspace, float* commands, float* args,
+                              int32_t* len_groups, int32_t* status, uint8_t* valid, void* stream) {
+    return svg_parse_launch<false>(data, B, offsets, kind, slot, P, N, G, S, workspace, commands, args, len_groups, status, valid,
+                                   stream);
+}
+
+extern "C" int dsvg_svg_parse_exact(const uint8_t* data, int64_t B, const int64_t* offsets, const uint8_t* kind,
+                                    const int32_t* slot, int64_t P, int64_t N, int32_t G, int32_t S, int32_t* workspace,
+                                    float* commands, float* args, int32_t* len_groups, int32_t* status, uint8_t* valid,
+                                    void* stream) {
+    return svg_parse_launch<true>(data, B, offsets, kind, slot, P, N, G, S, workspace, commands, args, len_groups, status, valid,
+                                  stream);
 }

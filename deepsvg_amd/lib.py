@@ -26,6 +26,8 @@ DSVG_SVG_PATH, DSVG_SVG_POLYLINE, DSVG_SVG_POLYGON = 0, 1, 2         # kinds of 
 (DSVG_SVG_OK, DSVG_SVG_EMPTY, DSVG_SVG_ARG_COUNT, DSVG_SVG_SLOW_NUMBER, DSVG_SVG_ROWS_OVERFLOW, DSVG_SVG_BAD_SLOT,
  DSVG_SVG_RANGE) = range(7)                                           # its status codes
 DSVG_SVG_TILE = 64                                                    # bytes of a string one wave reads at a time
+# the domain of the exact number rule (dsvg_svg_parse_exact): significant digits, and the decimal exponent of the last one
+DSVG_SVG_EXACT_DIGITS, DSVG_SVG_EXACT_E10_MIN, DSVG_SVG_EXACT_E10_MAX = 19, -64, 38
 # == DSVG_ABI_VERSION of include/dsvg.h at the time SIGNATURES below was written: load() refuses a library built from another
 # header (a stale .so with the old argument lists would otherwise be called with a stream where a size is expected)
 ABI_VERSION = 19
@@ -145,6 +147,7 @@ SIGNATURES = {
                                         c_i32, vp, vp, vp, vp]),
     "dsvg_paths_transform": (c_i32, [vp, vp, c_i64, c_i32, c_i32, c_i32, c_u32, vp, c_i32, vp, vp]),
     "dsvg_svg_parse": (c_i32, [vp, c_i64, vp, vp, vp, c_i64, c_i64, c_i32, c_i32, vp, vp, vp, vp, vp, vp, vp]),
+    "dsvg_svg_parse_exact": (c_i32, [vp, c_i64, vp, vp, vp, c_i64, c_i64, c_i32, c_i32, vp, vp, vp, vp, vp, vp, vp]),
     "dsvg_attention_causal_fwd": (c_i32, [c_i32, vp, vp, vp, c_i64, c_i32, c_i32, c_f32, c_f32, c_u32, vp, vp]),
     "dsvg_attention_causal_bwd": (c_i32, [c_i32, vp, vp, vp, vp, c_i64, c_i32, c_i32, c_f32, c_f32, c_u32, vp, vp]),
     "dsvg_seq_lens": (c_i32, [vp, c_i64, c_i32, c_i32, vp, vp]),

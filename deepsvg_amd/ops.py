@@ -1836,6 +1836,17 @@ def svg_parse(data, offsets, kind, slot, N, G, S):
     of deepsvg_amd.svgio.parse_paths: "commands" [N, G, S] / "args" [N, G, S, 11] float32, "len_groups" int32 [N, G],
     "status" int32 [P], "valid" bool [N].  Five launches (csrc/svg_parse.hip) and a workspace of 2 N G int32; nothing is read
     back; include/dsvg.h has the definition"""
+    return _svg_parse("dsvg_svg_parse", data, offsets, kind, slot, N, G, S)
+
+
+def svg_parse_exact(data, offsets, kind, slot, N, G, S):
+    """`svg_parse` with the exact number rule of include/dsvg.h: a number of up to 19 significant digits whose float32 value
+    is finite and not zero is converted on the device as Python's float() converts it, where `svg_parse` reports SLOW_NUMBER
+    for one outside its fast path.  Same arguments, same five launches (the parse kernel's other instantiation), same dict"""
+    return _svg_parse("dsvg_svg_parse_exact", data, offsets, kind, slot, N, G, S)
+
+
+def _svg_parse(symbol, data, offsets, kind, slot, N, G, S):
     _chk(data, offsets, kind, slot)
     assert data.dtype == torch.uint8 and data.dim() == 1 and data.is_contiguous()
     assert offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.numel() >= 2 and offsets.is_contiguous()
@@ -1855,9 +1866,9 @@ def svg_parse(data, offsets, kind, slot, N, G, S):
         B = 0
     else:
         B = data.numel()
-    _l.check(_l.load().dsvg_svg_parse(data.data_ptr(), B, offsets.data_ptr(), kind.data_ptr(), slot.data_ptr(), P, N, G, S,
-                                      ws.data_ptr(), out_c.data_ptr(), out_a.data_ptr(), len_groups.data_ptr(),
-                                      status.data_ptr(), valid.data_ptr(), _stream()), "dsvg_svg_parse")
+    _l.check(getattr(_l.load(), symbol)(data.data_ptr(), B, offsets.data_ptr(), kind.data_ptr(), slot.data_ptr(), P, N, G, S,
+                                        ws.data_ptr(), out_c.data_ptr(), out_a.data_ptr(), len_groups.data_ptr(),
+                                        status.data_ptr(), valid.data_ptr(), _stream()), symbol)
     return {"commands": out_c, "args": out_a, "len_groups": len_groups, "status": status, "valid": valid}
 
 

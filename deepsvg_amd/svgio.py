@@ -20,9 +20,16 @@ canonicalize -> simplify_heuristic(unit=1)``, composed from `paths`; `preprocess
 ``PackedSVGStore`` (``from_batch(viewbox=24)``) with the meta table of preprocess.py:26-32.  `to_svg` writes tensors as SVG
 text that `load_svgs` reads back bit for bit.
 
+Numbers: `parse_paths`, `load_svgs` and `preprocess_files` take ``numbers="fast"`` (the default: digits below 2^53 and a decimal
+exponent within 22, SLOW_NUMBER otherwise) or ``numbers="exact"`` (dsvg_svg_parse_exact: every number of up to 19 significant
+digits whose float32 value is finite and not zero, converted on the device with integers as ``float()`` converts it).  Files
+the reference itself saved - ``SVG.save_svg`` prints float32 values through float64 with up to 17 digits, so its docs/ and the
+output folder of dataset/preprocess.py - load with ``numbers="exact"``; tests/svgio_exact_ref.py restates that rule and
+tests/golden/svgio/exact.npz holds the reference's rows for long numbers.
+
 Out of scope: `transform=` attributes, styles, `<use>`, units and percentages, compact arc flags (`a1 1 0 01 2 2`: the
-reference reads `01` as one number and asserts, this reports ARG_COUNT), ``SVG.load_splineset``, and a host fallback for
-numbers outside the kernel's fast path (status SLOW_NUMBER).
+reference reads `01` as one number and asserts, this reports ARG_COUNT), ``SVG.load_splineset``, and numbers of more than 19
+significant digits (status SLOW_NUMBER under either rule).
 """
 import os
 from xml.dom import expatbuilder
@@ -65,7 +72,16 @@ def pack_strings(strings):
     return np.frombuffer(b"".join(raw), dtype=np.uint8).copy(), offsets
 
 
-def parse_paths(data, offsets=None, kind=None, slot=None, N=None, G=None, S=None, icon=None, device=None):
+def _entry(name, numbers):
+    """numbers = "fast" | "exact" -> the entry of `ops` that reads numbers that way"""
+    if numbers == "fast":
+        return ops.svg_parse
+    if numbers == "exact":
+        return ops.svg_parse_exact
+    raise ValueError(f'{name}: numbers is "fast" or "exact"; got {numbers!r}')
+
+
+def parse_paths(data, offsets=None, kind=None, slot=None, N=None, G=None, S=None, icon=None, device=None, numbers="fast"):
     """SVG path text -> padded rows, one call of csrc/svg_parse.hip.  Two forms:
       tensors on the device (nothing is read back): data uint8 [B], the UTF-8 bytes of P strings back to back; offsets int64
         [P + 1]; kind uint8 [P] (0 a `d` attribute, 1 the `points` of a polyline, 2 of a polygon); slot int32 [P], the output
@@ -78,7 +94,12 @@ def parse_paths(data, offsets=None, kind=None, slot=None, N=None, G=None, S=None
       "len_groups" int32 (N, G); "status" int32 [P], an index into `STATUS`; "valid" bool [N].
     An icon is valid when every string with a slot in it is OK or EMPTY; an invalid icon comes back as SOS, EOS... in every
     group, as `paths.split` hands one back.  A string whose slot is outside [-1, N G), or shared with another string, is
-    BAD_SLOT and is not parsed."""
+    BAD_SLOT and is not parsed.
+    numbers: "fast" (the default) converts a number whose digits are an integer below 2^53 with a decimal exponent of at most
+    22 either way, and reports SLOW_NUMBER for any other; "exact" converts every number of up to 19 significant digits whose
+    float32 value is finite and not zero, as Python's float() does - among them the 17-digit numbers ``SVG.save_svg`` prints.
+    Where both give a value it is the same one."""
+    entry = _entry("parse_paths", numbers)
     if isinstance(data, (list, tuple)):
         if offsets is not None or slot is not None:
             raise ValueError("parse_paths: a list of strings comes with `icon`, not with offsets or slot")
@@ -119,7 +140,7 @@ def parse_paths(data, offsets=None, kind=None, slot=None, N=None, G=None, S=None
         if data.numel() >= 2 ** 31:
             raise ValueError("parse_paths: 2^31 bytes of text or more in one call")
         data, offsets, kind, slot = (t.detach().contiguous() for t in (data, offsets, kind, slot))
-    return ops.svg_parse(data, offsets, kind, slot, N, G, S)
+    return entry(data, offsets, kind, slot, N, G, S)
 
 
 # ---- the document layer ------------------------------------------------------------------------------------------------------
@@ -180,7 +201,7 @@ def _document(text):
     return vb, [(tag, x, order[id(x)]) for tag in TAGS for x in dom.getElementsByTagName(tag)]
 
 
-def load_svgs(texts, max_num_groups=8, max_seq_len=30, device="cuda"):
+def load_svgs(texts, max_num_groups=8, max_seq_len=30, device="cuda", numbers="fast"):
     """A list of SVG documents (str) -> the model's padded tensors: ``SVG.from_str(text)`` with every group through
     ``to_path()`` for the whole list.  Groups are taken in the reference's order: all `path`, then `rect`, `circle`,
     `ellipse`, `line`, `polyline`, `polygon`, each in document order, nested elements included, `transform` ignored.  G =
@@ -192,7 +213,10 @@ def load_svgs(texts, max_num_groups=8, max_seq_len=30, device="cuda"):
       group's element among the icon's drawable elements in document order, -1 where the group is unused.
     An icon is invalid - SOS, EOS... in every group, "valid" false - when a string of it is, when it has more groups than
     max_num_groups, when a primitive needs more than max_seq_len rows, holds a value that is not finite or lacks a number it
-    needs, when its view box is not four finite numbers, or when the document does not parse."""
+    needs, when its view box is not four finite numbers, or when the document does not parse.  numbers: how `parse_paths` reads
+    the numbers of the text, "fast" or "exact" (a file ``SVG.save_svg`` wrote needs "exact"); the attributes of the other
+    primitives are read by float() on the host either way."""
+    _entry("load_svgs", numbers)
     if isinstance(texts, (str, bytes)) or len(texts) < 1:
         raise ValueError("load_svgs: texts is a non-empty list of SVG documents")
     N, G, S = _shape("load_svgs", len(texts), max_num_groups, max_seq_len + 2 if isinstance(max_seq_len, int) else max_seq_len)
@@ -242,7 +266,7 @@ def load_svgs(texts, max_num_groups=8, max_seq_len=30, device="cuda"):
     dev = torch.device(device)
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)       # noqa: E731
     res = parse_paths(up(host_data), up(host_off), up(np.asarray(kinds, dtype=np.uint8)), up(np.asarray(slots, dtype=np.int32)),
-                      N, G, S)
+                      N, G, S, numbers=numbers)
     valid = res["valid"] & up(host_valid)
     if rows_cmd:
         at = up(np.asarray(rows_at, dtype=np.int64))
@@ -330,11 +354,13 @@ def meta_table(ids, len_groups):
     return pd.DataFrame(records, columns=["id", "total_len", "nb_groups", "len_groups", "max_len_group"])
 
 
-def preprocess_files(files, max_num_groups=8, max_seq_len=30, device="cuda", batch_size=4096):
+def preprocess_files(files, max_num_groups=8, max_seq_len=30, device="cuda", batch_size=4096, numbers="fast"):
     """dataset/preprocess.py over SVG files: `load_svgs` and `preprocess` in batches of batch_size, the icons that stay valid
     (and are not empty) packed by ``PackedSVGStore.from_batch(viewbox=24)``.  -> (store, meta): the store's ids are the file
-    names without their extension, meta is `meta_table` over the same icons, in the same order."""
+    names without their extension, meta is `meta_table` over the same icons, in the same order.  numbers goes to `load_svgs`:
+    "exact" for files the reference saved (the output folder of its dataset/preprocess.py among them)."""
     from .dataset import PackedSVGStore
+    _entry("preprocess_files", numbers)
     files = list(files)
     if not files:
         raise ValueError("preprocess_files: no files")
@@ -345,7 +371,7 @@ def preprocess_files(files, max_num_groups=8, max_seq_len=30, device="cuda", bat
         for f in chunk:
             with open(f, "r", encoding="utf-8", errors="replace") as fh:      # a stray byte is a separator
                 texts.append(fh.read())
-        res = preprocess(load_svgs(texts, max_num_groups, max_seq_len, device))
+        res = preprocess(load_svgs(texts, max_num_groups, max_seq_len, device, numbers=numbers))
         keep = (res["valid"] & (res["n_groups"] > 0)).nonzero().view(-1)
         ids += [os.path.splitext(os.path.basename(chunk[i]))[0] for i in keep.tolist()]
         parts.append({k: res[k].index_select(0, keep) for k in ("commands", "args", "len_groups", "filling")})

@@ -66,7 +66,9 @@ extern "C" {
  *     Still 19: dsvg_raster_sweep_layers_nn / dsvg_raster_blend_bwd / dsvg_raster_sweep_layers_bwd /
  *     dsvg_raster_segments_layers_bwd added (the gradient of a layered image), on the same terms.
  *     Still 19: dsvg_svg_parse added (SVG path text to padded rows for a whole batch), on the same terms: four host tests pin 19
- *     for the bindings they cover, and no exported signature changed. */
+ *     for the bindings they cover, and no exported signature changed.
+ *     Still 19: dsvg_svg_parse_exact added (the same call with the exact number rule), on the same terms; dsvg_svg_parse keeps
+ *     its 16 parameters and its results. */
 #define DSVG_ABI_VERSION 19
 
 const char* dsvg_last_error(void);
@@ -1107,7 +1109,20 @@ int dsvg_assemble_augmented(const float* rows, int64_t n_rows, const int32_t* sl
  *  value: sign, then leading zeros and the trailing zeros of the fraction dropped, the remaining digits an integer w, e10 =
  *    exponent - fraction digits kept.  With w < 2^53 and |e10| <= 22 the value is (double)w * 10^e10 (e10 >= 0) or (double)w /
  *    10^-e10: one correctly rounded operation on exact operands, equal to strtod / Python's float() bit for bit; -0 keeps its
- *    sign.  Anything else (more digits, an accumulator past 2^64, a larger exponent) is DSVG_SVG_SLOW_NUMBER.
+ *    sign.  Anything else (more digits, an accumulator past 2^64, a larger exponent) is DSVG_SVG_SLOW_NUMBER.  This is the
+ *    FAST RULE, the rule of dsvg_svg_parse.
+ *  value, the EXACT RULE (dsvg_svg_parse_exact; csrc/decimal_exact.h, restated in tests/svgio_exact_ref.py): the digit string
+ *    (integer and fraction digits, the dot removed) is stripped of its leading zeros and of its trailing zeros, and every
+ *    stripped trailing zero, integer or fractional, raises the exponent by one.  What is left is an integer w of nd digits
+ *    and e10 = written exponent (saturated as above) - fraction digits + stripped trailing zeros.  w == 0 is a zero of the
+ *    number's sign, whatever the exponent.  Otherwise, with nd <= DSVG_SVG_EXACT_DIGITS and DSVG_SVG_EXACT_E10_MIN <= e10 <=
+ *    DSVG_SVG_EXACT_E10_MAX, the value is the float64 nearest to w * 10^e10, ties to even: strtod / Python's float() bit for
+ *    bit, formed with integers only (w < 10^19 < 2^64 is one word, 5^38 and 5^64 fit 89 and 149 bits, every result is a normal
+ *    float64 between 1e-64 and 1e57).  Anything else is DSVG_SVG_SLOW_NUMBER.  A number below the domain is zero in fp32 and one
+ *    above it is infinite there: the domain holds every number of at most 19 significant digits whose fp32 value is finite and
+ *    not zero.  Where the fast rule gives a value the exact rule gives the same one; it only turns some SLOW_NUMBERs into
+ *    values.  Everything else - tokens, the first error in reading order, numbers in front of the first letter never
+ *    converted, RANGE, the fp32 position arithmetic, the counts - is the same for both entries.
  *  commands: per letter with k numbers behind it.  z: k = 0, and the position returns to the sub-path's initial position.
  *    Any other letter: k > 0 and a multiple of its arity (m l t 2; h v 1; c 6; s q 4; a 7), k / arity commands; k = 0 is
  *    DSVG_SVG_ARG_COUNT like every other miscount (the reference indexes its empty command list and raises).  An m with more
@@ -1144,6 +1159,13 @@ int dsvg_assemble_augmented(const float* rows, int64_t n_rows, const int32_t* sl
 int dsvg_svg_parse(const uint8_t* data, int64_t B, const int64_t* offsets, const uint8_t* kind, const int32_t* slot,
                    int64_t P, int64_t N, int32_t G, int32_t S, int32_t* workspace, float* commands, float* args,
                    int32_t* len_groups, int32_t* status, uint8_t* valid, void* stream);
+/* The same call - arguments, launches, outputs - with the exact rule for the value of a number. */
+#define DSVG_SVG_EXACT_DIGITS 19
+#define DSVG_SVG_EXACT_E10_MIN (-64)
+#define DSVG_SVG_EXACT_E10_MAX 38
+int dsvg_svg_parse_exact(const uint8_t* data, int64_t B, const int64_t* offsets, const uint8_t* kind, const int32_t* slot,
+                         int64_t P, int64_t N, int32_t G, int32_t S, int32_t* workspace, float* commands, float* args,
+                         int32_t* len_groups, int32_t* status, uint8_t* valid, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Fused FFN sub-block, bf16, d_model = 256 / dim_feedforward = 512 (csrc/ffn_fused.hip):
